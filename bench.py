@@ -8,7 +8,14 @@ processors -> segment extraction on the host -> RCCL all-gather of the per-windo
 Weights are large-v3-turbo-shaped, seeded synthetic (no checkpoints offline). Each rank processes its own
 B windows (chunk data parallelism, weak scaling); value = total audio seconds of all ranks / step time.
 
-    python bench.py [--gpus N --steps K --warmup W --batch B --decode-tokens T --no-cpu-baseline]
+    python bench.py [--gpus N --steps K --warmup W --batch B --decode-tokens T] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, ...).
+--full adds everything else the line has carried: the per-launch HIP-event timing of the dominant GEMM family inside
+the timed region and the roofline figures from it, the decoder cross-attention roofline (an eager decode step of its
+own), the parity check against the fp32 goldens and the transformers CPU baseline. --dump-outputs DIR writes what the
+last timed step returned to its caller as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -50,7 +57,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=0, help="windows per GPU (default 24 for c2, 64 for c5)")
     ap.add_argument("--decode-tokens", type=int, default=128)
     ap.add_argument("--model", default="large-v3-turbo")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-launch kernel timing and "
+                         "the roofline figures, the decode cross-attention roofline, parity against the fp32 goldens, "
+                         "the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (tokens, token counts, "
+                         "language ids; c3: segment timestamps too) as DIR/<name>.npy")
     ap.add_argument("--force-collective", action="store_true",
                     help="N = 1: run the RCCL path anyway (an nccl group of one; the per-batch token all-gather, c3's "
                          "waveform broadcast and sharded call)")
@@ -59,7 +73,10 @@ def parse():
     ap.add_argument("--eos", action="store_true",
                     help="free-running decode (SURVEY §8d, reported separately): EOS not suppressed, each window stops "
                          "at its EOS or after --decode-tokens; the roofline accounting's fixed length is the default")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def launch_plan(gpus: int, env) -> str:
@@ -158,17 +175,23 @@ def main():
         audio = workload(B, 30.0, seed=1234 + 1000 * rank)
         eng.wave[:B].copy_(torch.from_numpy(audio))
 
+    last = {}  # what the last run() handed back beside its tokens (for --dump-outputs)
+
     def run(n_steps):
         if strong:  # one step = one full call: host waveform -> broadcast -> shard -> batches -> gather -> text
             out = None
             for _ in range(n_steps):
                 out = tr(hour, **call_kw)
+            last["call"] = out
             return [p for w in tr.last_window_passes for p in w[:1]] if out is not None else []
         """n_steps batches of B windows through the engine's two-slot pipeline (the encoder of batch k+1 runs on
         a second HIP stream beside the decode of batch k); every rank then all-gathers each batch's tokens."""
         res = eng.run_batches([B] * n_steps, task="transcribe", max_new_tokens=T, max_passes=1)
         if world > 1 or forced:  # rank r holds windows [rB, (r+1)B) of each batch: one RCCL all-gather per batch
-            res = [twd.gather_tokens(seqs, lg, world * B)[0] for seqs, lg in zip(res, eng.batch_langs)]
+            both = [twd.gather_tokens(seqs, lg, world * B) for seqs, lg in zip(res, eng.batch_langs)]
+            res, last["langs"] = [g[0] for g in both], (both[-1][1] if both else [])
+        else:
+            last["langs"] = eng.batch_langs[-1] if res else []
         return res[-1] if res else []
 
     run(a.warmup)
@@ -188,8 +211,10 @@ def main():
     # HIP events around every launch of the dominant kernel (k_gemm_big) on the engine stream, inside the
     # timed region (the encoder is not graph-captured; ~0.3 us per event against 0.2-1 ms per launch)
     # (TW_BENCH_EXTRA_FAMILIES="attn_encoder,...": further families timed the same way and listed in kernel_families)
+    # (--full only: the headline figure needs no events)
     extra = {f for f in os.environ.get("TW_BENCH_EXTRA_FAMILIES", "").split(",") if f}
-    eng.timers, eng.timer_families = ({}, {dom} | extra) if os.environ.get("TW_BENCH_TIMERS", "1") != "0" else (None, None)
+    timed = a.full and os.environ.get("TW_BENCH_TIMERS", "1") != "0"
+    eng.timers, eng.timer_families = ({}, {dom} | extra) if timed else (None, None)
     t0 = time.perf_counter()
     seqs = run(a.steps)
     torch.cuda.synchronize()
@@ -198,6 +223,8 @@ def main():
     dt = time.perf_counter() - t0
     fam = eng.timer_summary()
     eng.timers, eng.timer_families = None, None
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, seqs, tr.last_window_langs if strong else last["langs"], last.get("call"))
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=eng.device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -210,26 +237,6 @@ def main():
     audio_s = (120 // max(1, a.c3_share)) * 30.0 if strong else world * B * 30.0
     rtf = audio_s / (dt / a.steps)
     n_tok = [len(s) for s in seqs]
-
-    # dominant kernel: all k_gemm_big launches of the timed steps (every epilogue variant)
-    dfam = [v for k, v in fam.items() if k[0] == dom]
-    n_l = max(1, sum(v[0] for v in dfam))  # (0 with TW_BENCH_TIMERS=0: A/B runs without events)
-    work = sum(v[1] for v in dfam)
-    tot_ms = sum(v[2] for v in dfam)
-    avg_ms = max(tot_ms / n_l, 1e-9)
-    achieved = (work / n_l) / (avg_ms * 1e-3) / 1e12
-    families = {f"{k[0]}<{k[1]}>": {"launches": v[0], "tflop": round(v[1] / 1e12, 3), "ms": round(v[2], 3),
-                                    "tflops": round(v[1] / (v[2] * 1e-3) / 1e12, 1) if v[2] > 0 else None}
-                for k, v in fam.items()}
-    # the bf16 family runs as k_gemm_big beside a decode and as k_gemm_8p alone (engine._set_gemm_context)
-    # (the MX family: k_gemm_8p_mx on every encoder shape since round 5, k_gemm_mx before and on request)
-    fam_k = ("k_gemm_mx", "k_gemm_8p_mx") if fp8 else ("k_gemm_big", "k_gemm_8p", "k_gemm_8pp")
-    traffic, traffic_src = measured_traffic(fam_k, fp8)
-    mfma_busy, mfma_src = measured_mfma(fam_k, fp8)
-
-    # secondary (HBM-bound) kernel: decoder cross-attention, timed on one eager decode pass outside the timed
-    # region (the timed decode steps replay a hipGraph, which has no room for events)
-    dec = decode_cross_roofline(eng, B, traffic_lookup=measured_traffic(("k_attn_decode_cross",), fp8))
 
     out = {
         "metric": "real-time factor (audio-sec/wall-sec) Whisper-v3-turbo, 30s chunks, 1/2/4/8 GPU",
@@ -260,31 +267,77 @@ def main():
                                   ("rccl (group of one, forced)" if forced else "none"),
                    "global_batch": int(audio_s // 30), "seq_len": 3000, "parallelism": f"chunk-dp{world}",
                    "decode_tokens_per_window": T, "mean_tokens_out": float(np.mean(n_tok))},
-        "roofline": {"bound": "mfma",
-                     "kernel": ("k_gemm_8p_mx / k_gemm_mx (encoder q/k/v/o + fc1/fc2, MX fp8 MFMA)" if fp8 else
-                                "k_gemm_big / k_gemm_8p / k_gemm_8pp (all encoder/conv/cross-KV projections, bf16 MFMA)"),
-                     "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4), "traffic": traffic,
-                     "traffic_source": traffic_src, "mfma_busy_pct": mfma_busy, "mfma_source": mfma_src,
-                     "launches_per_step": n_l // a.steps,
-                     "avg_launch_ms": round(avg_ms, 4), "flop_per_launch": work / n_l},
-        "roofline_decode": dec,
-        "parity": None,
-        "kernel_families": families,
-        "cpu_baseline": None,
+        "full": a.full,
     }
-    if rank == 0:
-        out["parity"], out["parity_detail"] = (parity_vs_golden(eng, B, T, a.model, fp8) if not strong and not a.eos else
-                                               (None, {"skipped": "free-running decode: the golden is the EOS-suppressed "
-                                                                  "decode"}) if a.eos else
-                                               (None, {"skipped": "c3 windows differ from the golden's; the same "
-                                                                  "engine's parity is the c2 line's"}))
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(dims, gen, T, a.cpu_threads)
+    if a.full:
+        # dominant kernel: all k_gemm_big launches of the timed steps (every epilogue variant)
+        dfam = [v for k, v in fam.items() if k[0] == dom]
+        n_l = max(1, sum(v[0] for v in dfam))  # (0 with TW_BENCH_TIMERS=0: A/B runs without events)
+        work = sum(v[1] for v in dfam)
+        tot_ms = sum(v[2] for v in dfam)
+        avg_ms = max(tot_ms / n_l, 1e-9)
+        achieved = (work / n_l) / (avg_ms * 1e-3) / 1e12
+        families = {f"{k[0]}<{k[1]}>": {"launches": v[0], "tflop": round(v[1] / 1e12, 3), "ms": round(v[2], 3),
+                                        "tflops": round(v[1] / (v[2] * 1e-3) / 1e12, 1) if v[2] > 0 else None}
+                    for k, v in fam.items()}
+        # the bf16 family runs as k_gemm_big beside a decode and as k_gemm_8p alone (engine._set_gemm_context)
+        # (the MX family: k_gemm_8p_mx on every encoder shape since round 5, k_gemm_mx before and on request)
+        fam_k = ("k_gemm_mx", "k_gemm_8p_mx") if fp8 else ("k_gemm_big", "k_gemm_8p", "k_gemm_8pp")
+        traffic, traffic_src = measured_traffic(fam_k, fp8)
+        mfma_busy, mfma_src = measured_mfma(fam_k, fp8)
+
+        # secondary (HBM-bound) kernel: decoder cross-attention, timed on one eager decode pass outside the timed
+        # region (the timed decode steps replay a hipGraph, which has no room for events)
+        dec = decode_cross_roofline(eng, B, traffic_lookup=measured_traffic(("k_attn_decode_cross",), fp8))
+        out.update({
+            "roofline": {"bound": "mfma",
+                         "kernel": ("k_gemm_8p_mx / k_gemm_mx (encoder q/k/v/o + fc1/fc2, MX fp8 MFMA)" if fp8 else
+                                    "k_gemm_big / k_gemm_8p / k_gemm_8pp (all encoder/conv/cross-KV projections, bf16 MFMA)"),
+                         "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
+                         "frac": round(achieved / peak, 4), "traffic": traffic,
+                         "traffic_source": traffic_src, "mfma_busy_pct": mfma_busy, "mfma_source": mfma_src,
+                         "launches_per_step": n_l // a.steps,
+                         "avg_launch_ms": round(avg_ms, 4), "flop_per_launch": work / n_l},
+            "roofline_decode": dec,
+            "parity": None,
+            "kernel_families": families,
+            "cpu_baseline": None,
+        })
+        if rank == 0:
+            out["parity"], out["parity_detail"] = (parity_vs_golden(eng, B, T, a.model, fp8) if not strong and not a.eos else
+                                                   (None, {"skipped": "free-running decode: the golden is the EOS-suppressed "
+                                                                      "decode"}) if a.eos else
+                                                   (None, {"skipped": "c3 windows differ from the golden's; the same "
+                                                                      "engine's parity is the c2 line's"}))
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(dims, gen, T, a.cpu_threads)
     if rank == 0:
         print(json.dumps(out))
     if world > 1 or forced:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, seqs, langs, call=None):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 arrays under `path`.
+    tokens.npy (windows x longest sequence, float32, -1 past a window's end; token ids are exact in float32),
+    token_counts.npy, languages.npy (the detected language token per window, -1 for none); for a TurboTranscriber
+    call (c3) also timestamps.npy (segments x 2, float64 seconds, NaN for an open end) and text_codepoints.npy (the
+    transcript's characters). The workload and the weights are seeded, so the same arguments give the same inputs in
+    every run. (A few hundred KB at most: 120 windows x 128 tokens.)"""
+    os.makedirs(path, exist_ok=True)
+    n = max([len(s) for s in seqs], default=0)
+    tok = np.full((len(seqs), n), -1.0, np.float32)
+    for i, s in enumerate(seqs):
+        tok[i, :len(s)] = s
+    arrays = {"tokens": tok, "token_counts": np.array([len(s) for s in seqs], np.float32),
+              "languages": np.array([-1 if lg is None else lg for lg in langs], np.float32)}
+    if call is not None:
+        ts = [c.get("timestamp") or (None, None) for c in call.get("chunks", [])]
+        arrays["timestamps"] = np.array([[np.nan if t is None else t for t in p] for p in ts],
+                                        np.float64).reshape(-1, 2)
+        arrays["text_codepoints"] = np.array([ord(c) for c in call.get("text", "")], np.float32)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def parity_vs_golden(eng, B, T, model, fp8):

@@ -19,7 +19,7 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/$
 rc2=$?
 echo "[$(date +%T)] smoke rc=$rc2"; tail -2 $OUT/${TAG}_smoke.txt
 if [ $rc2 -ne 0 ]; then echo "STOP after smoke"; exit $rc2; fi
-timeout -k 10 600 python -u bench.py --steps 10 --warmup 3 ${BENCH_ARGS:---no-cpu-baseline} > $OUT/${TAG}_bench.txt 2>&1
+timeout -k 10 600 python -u bench.py --steps 10 --warmup 3 ${BENCH_ARGS:---full --no-cpu-baseline} > $OUT/${TAG}_bench.txt 2>&1
 rc3=$?
 echo "[$(date +%T)] bench rc=$rc3"; grep '^{' $OUT/${TAG}_bench.txt | tail -1 | cut -c1-600
 exit $(( rc != 0 ? rc : rc3 ))

@@ -15,7 +15,7 @@ step() {  # step NAME TIMEOUT CMD...
   if [ $rc -ne 0 ]; then echo "STOP after $name"; exit $rc; fi
   grep '^{' $OUT/$name.log | tail -1 > $OUT/$name.json
 }
-step c3_full 900 python -u bench.py --config c3 --steps 5 --warmup 2 --no-cpu-baseline
-step c3_share8 900 python -u bench.py --config c3 --c3-share 8 --steps 10 --warmup 3 --no-cpu-baseline
-step c5 900 python -u bench.py --config c5 --steps 10 --warmup 3 --no-cpu-baseline
+step c3_full 900 python -u bench.py --config c3 --steps 5 --warmup 2 --full --no-cpu-baseline
+step c3_share8 900 python -u bench.py --config c3 --c3-share 8 --steps 10 --warmup 3 --full --no-cpu-baseline
+step c5 900 python -u bench.py --config c5 --steps 10 --warmup 3 --full --no-cpu-baseline
 echo done

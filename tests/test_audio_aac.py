@@ -26,7 +26,8 @@ from oracle import aac_oracle as ao
 from oracle import mp3_oracle as mo
 from twamd import _lib, audio
 
-IMAGES = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/"
+MEDIA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "media")  # small real-encoder files
+IMAGES = os.path.join(MEDIA, "")
 REALSHORT, COCKATOO = IMAGES + "realshort.mp4", IMAGES + "cockatoo.mp4"
 REL = 1e-6
 

@@ -24,7 +24,8 @@ import pytest
 from oracle import mp3_oracle as mo
 from twamd import _lib, audio
 
-A11Y = "/usr/local/lib/python3.10/dist-packages/kaleido/executable/etc/mathjax/extensions/a11y/"
+MEDIA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "media")  # small real-encoder files
+A11Y = os.path.join(MEDIA, "")
 REAL_MP3, REAL_OGG = A11Y + "invalid_keypress.mp3", A11Y + "invalid_keypress.ogg"
 REL = 1e-6
 real = pytest.mark.skipif(not os.path.exists(REAL_MP3), reason="the image's MathJax MP3 file is not present")

@@ -17,7 +17,8 @@ import pytest
 from oracle import vorbis_oracle as vo
 from twamd import _lib, audio
 
-REAL_OGG = "/usr/local/lib/python3.10/dist-packages/kaleido/executable/etc/mathjax/extensions/a11y/invalid_keypress.ogg"
+MEDIA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "media")  # small real-encoder files
+REAL_OGG = os.path.join(MEDIA, "invalid_keypress.ogg")
 REL = 1e-6
 
 

@@ -17,7 +17,8 @@ import pytest
 
 from twamd import audio
 
-DATA = "/usr/local/lib/python3.10/dist-packages/scipy/io/tests/data/"
+MEDIA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "media")  # small real-encoder files
+DATA = os.path.join(MEDIA, "wav", "")
 FILES = sorted(glob.glob(DATA + "test-*.wav"))
 REFUSED = {"36bit", "45bit", "53bit"}  # 5-7-byte containers: no ffmpeg PCM codec
 

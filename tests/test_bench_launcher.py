@@ -83,3 +83,35 @@ def test_warmup_completion_covers_every_timed_graph():
             have = bench.decode_graph_keys(warmup) | bench.decode_graph_keys(extra)
             assert bench.decode_graph_keys(steps) <= have, (steps, warmup, extra)
             assert extra <= 4
+
+
+def test_plain_run_is_the_default_and_steps_are_checked(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: ragged token lists become one -1 padded float32 matrix (token ids are exact in float32), with
+    the counts and language ids beside it; a TurboTranscriber call adds its segment timestamps and text."""
+    import numpy as np
+
+    d = str(tmp_path / "out")
+    bench.dump_outputs(d, [[50258, 50259, 51864], [7]], [50259, None],
+                       {"text": "hé", "chunks": [{"timestamp": (0.0, 1.5), "text": "h"},
+                                                 {"timestamp": (1.5, None), "text": "é"}]})
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    assert sorted(got) == ["languages", "text_codepoints", "timestamps", "token_counts", "tokens"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert got["tokens"].tolist() == [[50258, 50259, 51864], [7, -1, -1]]
+    assert got["token_counts"].tolist() == [3, 1] and got["languages"].tolist() == [50259, -1]
+    assert got["timestamps"].shape == (2, 2) and np.isnan(got["timestamps"][1, 1]) and got["timestamps"][1, 0] == 1.5
+    assert "".join(chr(int(c)) for c in got["text_codepoints"]) == "hé"
+    bench.dump_outputs(d, [], [])  # nothing decoded: empty arrays, no error
+    assert np.load(os.path.join(d, "tokens.npy")).shape == (0, 0)

@@ -9,8 +9,8 @@ out-of-bounds access, leak or undefined behaviour aborts the run. The corpus: th
 subframe kind / stereo mode / bit depth / blocking, its random-syntax Vorbis writer, the image's one libVorbis
 stream, the MP3 oracle's random-syntax Layer III writer (MPEG-1 / 2 / 2.5, every channel mode, Info + LAME frames,
 ID3v2 tags, junk between frames) and its Layer I / II writer, the image's one real MP3, the AAC oracle's random-syntax ADTS streams, the access
-units of the image's one real AAC-LC track as ADTS, and the reference's example FLAC (first 256 KB, when present in
-this container)."""
+units of the image's one real AAC-LC track as ADTS, and the reference's example FLAC (first 256 KB). The real files
+are stored under tests/golden/media/."""
 import os
 import subprocess
 
@@ -25,10 +25,11 @@ from oracle import vorbis_oracle as vo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "turbo-whisper-workspace_amd", "csrc")
-REAL_OGG = "/usr/local/lib/python3.10/dist-packages/kaleido/executable/etc/mathjax/extensions/a11y/invalid_keypress.ogg"
+MEDIA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "media")  # small real-encoder files
+REAL_OGG = os.path.join(MEDIA, "invalid_keypress.ogg")
 REAL_MP3 = REAL_OGG[:-3] + "mp3"
-REAL_AAC_MP4 = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
-REF_FLAC = "/root/reference/examples/Test1/ChrisAndAlexDiTest.flac"
+REAL_AAC_MP4 = os.path.join(MEDIA, "realshort.mp4")
+REF_FLAC_PREFIX = os.path.join(MEDIA, "ref_prefix.flac")  # the first 256 KB of the reference's example FLAC
 
 
 def _corpus(tmp_path):
@@ -74,8 +75,7 @@ def _corpus(tmp_path):
             adts += bytes([0xFF, 0xF1, 0x4C, 0x40 | (fl >> 11), (fl >> 3) & 0xFF, ((fl & 7) << 5) | 0x1F, 0xFC])
             adts += data[o: o + sz]
         put("real_aac.aac", adts)
-    if os.path.exists(REF_FLAC):
-        put("ref_prefix.flac", open(REF_FLAC, "rb").read()[: 256 * 1024])
+    put("ref_prefix.flac", open(REF_FLAC_PREFIX, "rb").read())
     put("adpcm_like.bin", rng.integers(0, 256, size=4096, dtype=np.uint8))
     tone = np.round(9000 * np.sin(np.arange(3000) / 7.0)).astype(np.int16)
     put("ms_adpcm.bin", ao.ms_adpcm_encode(np.stack([tone, tone[::-1]], 1), 2, 256, np.random.default_rng(2)))

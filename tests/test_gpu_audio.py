@@ -1,6 +1,8 @@
 """Audio ingest on the MI355X: the GPU resampler (tw_resample_pcm_*) against the oracle's float64 restatement of
 libswresample's default filter, and FLAC / Ogg Vorbis / MP3 (and MPEG Layers I / II) / AAC (M4A, ADTS) / ALAC files through
 the full product path (host decode -> GPU resample -> transcription). Tolerance: 2e-6 absolute on [-1, 1] signals (float32 accumulation of <= 396 taps)."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -11,6 +13,7 @@ from twamd.synth_audio import speech_like
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-6
+MEDIA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "media")  # small real-encoder files
 
 
 def _sig(sr, seconds, ch, seed):
@@ -67,7 +70,7 @@ def test_ogg_vorbis_bytes_through_load_input():
 
     from oracle import vorbis_oracle as vo
 
-    real = "/usr/local/lib/python3.10/dist-packages/kaleido/executable/etc/mathjax/extensions/a11y/invalid_keypress.ogg"
+    real = os.path.join(MEDIA, "invalid_keypress.ogg")
     streams = [open(real, "rb").read()] if os.path.exists(real) else []
     streams.append(vo.write_stream(np.random.default_rng(7), channels=2, bs_exp=(7, 9), n_packets=14, rate=44100))
     for data in streams:
@@ -87,7 +90,7 @@ def test_mp3_bytes_through_load_input():
 
     from oracle import mp3_oracle as mo
 
-    a11y = "/usr/local/lib/python3.10/dist-packages/kaleido/executable/etc/mathjax/extensions/a11y/"
+    a11y = os.path.join(MEDIA, "")
     streams = [open(a11y + "invalid_keypress.mp3", "rb").read()] if os.path.exists(a11y + "invalid_keypress.mp3") else []
     streams.append(mo.write_stream(np.random.default_rng(8), version=2, sr_sub=0, mode=1, nframes=12))
     for data in streams:
@@ -159,7 +162,7 @@ def test_mp3_file_through_process_audio(tmp_path):
     from twamd.audio_pipeline import AudioProcessingPipeline
     from twamd.pipeline import TurboTranscriber
 
-    real = "/usr/local/lib/python3.10/dist-packages/kaleido/executable/etc/mathjax/extensions/a11y/invalid_keypress.mp3"
+    real = os.path.join(MEDIA, "invalid_keypress.mp3")
     data = open(real, "rb").read() if os.path.exists(real) else mo.write_stream(np.random.default_rng(9), mode=1)
     path = str(tmp_path / "upload.mp3")
     with open(path, "wb") as f:
@@ -191,7 +194,7 @@ def test_aac_bytes_through_load_input():
 
     from oracle import aac_oracle as aao
 
-    real = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
+    real = os.path.join(MEDIA, "realshort.mp4")
     cases = []
     if os.path.exists(real):
         data = open(real, "rb").read()
@@ -218,7 +221,7 @@ def test_m4a_file_through_process_audio(tmp_path):
     from twamd.audio_pipeline import AudioProcessingPipeline
     from twamd.pipeline import TurboTranscriber
 
-    real = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
+    real = os.path.join(MEDIA, "realshort.mp4")
     data = open(real, "rb").read() if os.path.exists(real) else aao.write_mp4(np.random.default_rng(3))[0]
     path = str(tmp_path / "upload.m4a")
     with open(path, "wb") as f:
@@ -284,7 +287,7 @@ def test_ogg_file_through_process_audio(tmp_path):
     from twamd.audio_pipeline import AudioProcessingPipeline
     from twamd.pipeline import TurboTranscriber
 
-    real = "/usr/local/lib/python3.10/dist-packages/kaleido/executable/etc/mathjax/extensions/a11y/invalid_keypress.ogg"
+    real = os.path.join(MEDIA, "invalid_keypress.ogg")
     data = open(real, "rb").read() if os.path.exists(real) else vo.write_stream(np.random.default_rng(9), channels=2)
     path = str(tmp_path / "upload.ogg")
     with open(path, "wb") as f:

@@ -106,8 +106,8 @@ def test_bench_force_collective_line():
     device-tensor all-gather per batch) prints a line that says so, with parity true."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-collective", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=280, env=env,
-                       cwd=ROOT)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=280,
+                       env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["config"]["collectives"] == "rccl (group of one, forced)"
