@@ -207,6 +207,9 @@ typedef struct TwBeamParams {
   int32_t max_new;       /* max_length - prompt length                                   */
   float length_penalty;  /* generation_config.length_penalty (1.0)                       */
   int32_t ld_tokens;     /* row stride of tokens / fin_tokens (<= 448)                   */
+  int32_t scores_are_logprobs; /* 0: `logits` are raw and the step subtracts their logsumexp (log_softmax);
+                          * 1: tw_logits_history(to_logprobs) already rewrote them to processed
+                          * log-probabilities, taken as they are                          */
 } TwBeamParams;
 typedef struct TwBeamState {
   float* run_score;      /* f32[R]   running beam scores (descending within a window)    */
@@ -449,6 +452,23 @@ int tw_logits_sample(const float* logits, int B, int ld_logits, const uint32_t* 
 /* state[b][TW_ST_NOSPEECH] (f32 bits) = softmax(logits[b][0:V])[token]: WhisperNoSpeechDetection's no_speech_prob
  * ($TF/generation/logits_process.py:2050-2112) from the logits at the <|startoftranscript|> position. */
 int tw_token_prob(const float* logits, int B, int ld_logits, int V, int token, int* state, void* stream);
+
+/* RepetitionPenaltyLogitsProcessor then NoRepeatNGramLogitsProcessor ($TF/generation/logits_process.py), in place on
+ * rows [0, R) of f32 logits, ahead of tw_logits_select / _select_embed / _sample / tw_beam_step (generate() puts both
+ * in front of the Whisper processors). The history of row r is prefix[r][0 .. prefix_len[r]) (the decoder_input_ids
+ * the pass started from: prompt or previous segments with their left pads, <|startoftranscript|>, language, task,
+ * <|notimestamps|>; a prefix entry TW_HIST_LANG reads state[r][TW_ST_LANG], the language the mode-1 selection
+ * detected) followed by tokens[r][0 .. state[r][TW_ST_NGEN]); at most TW_HIST_MAX ids. prefix / prefix_len may both
+ * be NULL. repetition_penalty p (1.0 = off): every distinct id of the history gets y < 0 ? y * p : y / p (IEEE f32,
+ * from the value before any penalty). no_repeat_ngram n (0 = off): with L >= n ids, every id that followed an earlier
+ * occurrence of the last n - 1 ids becomes -inf (after the penalty). to_logprobs != 0: the row is first rewritten to
+ * x - logsumexp(x[0:V]) (beam search: set TwBeamParams.scores_are_logprobs). Rows with state[r][TW_ST_FINISHED] and
+ * columns [V, ld_logits) are left untouched; state and tokens are only read. */
+#define TW_HIST_MAX 448
+#define TW_HIST_LANG (-1)
+int tw_logits_history(float* logits, int R, int ld_logits, int V, const int* prefix, int ld_prefix,
+                      const int* prefix_len, const int* tokens, int ld_tokens, const int* state,
+                      float repetition_penalty, int no_repeat_ngram, int to_logprobs, void* stream);
 
 #ifdef __cplusplus
 }

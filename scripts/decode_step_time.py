@@ -3,11 +3,15 @@ decoder step (47 launches per token), for several row counts. One pass = the pro
 detection, task token) + 128 generated tokens with EOS suppressed, i.e. 130 decoder steps; the encoder runs once
 before, untimed. Prints one JSON line per (rows, mode).
 
-    python scripts/decode_step_time.py [--rows 15 24 64] [--reps 3] [--fused 0 1]
+    python scripts/decode_step_time.py [--rows 15 24 64] [--reps 3] [--fused 0 1] [--penalties 0 1] [--beams 12 5]
 
 --fused 1: the decoder's layers as one persistent launch (tw_dec_fused) at every row count <= 32, 0: the launch chain
 (WhisperEngine.dec_fused_alone / dec_fused_max_rows overridden); with both, each row count runs both and reports
 whether their tokens agree.
+--penalties 1: the passes run with repetition_penalty=1.3 and no_repeat_ngram_size=3 (tw_logits_history queued ahead
+of every selection), 0: without; with both, the cost of the pre-pass is the difference of the two lines.
+--beams W NB: also the beam pass of W windows x NB beams (one captured step per token: decoder step over W * NB rows,
+tw_beam_step), 128 tokens with EOS suppressed, per step from the pass's wall time.
 """
 import argparse
 import json
@@ -34,11 +38,14 @@ def main():
     ap.add_argument("--fused", type=int, nargs="+", default=[0])
     ap.add_argument("--slope", type=int, default=0, help="also time 64-token passes: per-step slope without the "
                     "pass's fixed costs")
+    ap.add_argument("--penalties", type=int, nargs="+", default=[0])
+    ap.add_argument("--beams", type=int, nargs=2, default=None, metavar=("W", "NB"))
     a = ap.parse_args()
     dims = PRESETS["large-v3-turbo"]
     gen = GenerationSettings.default(dims)
-    B = max(a.rows)
-    eng = WhisperEngine(build_weights(dims, seed=1234), gen, max_batch=B, device="cuda")
+    B = max(a.rows + ([a.beams[0]] if a.beams else []))
+    eng = WhisperEngine(build_weights(dims, seed=1234), gen, max_batch=B, device="cuda",
+                        max_beams=a.beams[1] if a.beams else 1)
     eng.set_suppress_tokens(list(gen.suppress_tokens) + [gen.special.eot])
     eng.wave[:B].copy_(torch.from_numpy(workload(B, 30.0, seed=1234)))
     eng.logmel(B)
@@ -48,47 +55,67 @@ def main():
         eng.seek[:R] = 0
         eng.encode(R)
         torch.cuda.synchronize()
-        ref = None
-        for fz, ce, gs in [(f, c, g) for f in a.fused for c in a.check_every for g in a.graph_steps]:
+        ref = {}  # per penalties value: the first mode's tokens
+        for fz, ce, gs, pen in [(f, c, g, p) for f in a.fused for c in a.check_every for g in a.graph_steps
+                                for p in a.penalties]:
             if fz and R > 32:
                 continue
             eng.dec_fused_alone = bool(fz)
             eng.dec_fused_max_rows = 32 if fz else 0
             eng.graph_steps_alone = gs
             eng._graphs.clear()
-            eng.decode_pass(R, tail, None, 128, check_every=ce)  # warm-up: graph captures
+            hk = {"repetition_penalty": 1.3, "no_repeat_ngram_size": 3} if pen else {}
+            eng.decode_pass(R, tail, None, 128, check_every=ce, **hk)  # warm-up: graph captures
             torch.cuda.synchronize()
             best = 1e9
             eng.pass_events = []
             for _ in range(a.reps):
                 t0 = time.perf_counter()
-                res = eng.decode_pass(R, tail, None, 128, check_every=ce)
+                res = eng.decode_pass(R, tail, None, 128, check_every=ce, **hk)
                 torch.cuda.synchronize()
                 best = min(best, time.perf_counter() - t0)
             loop_us = min(e0.elapsed_time(e1) * 1e3 / n for e0, e1, n, _ in eng.pass_events)
             eng.pass_events = None
-            print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs,
+            print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs, "penalties": pen,
                               "loop_us_per_step": round(loop_us, 1)}),
                   flush=True)
             assert all(len(t) == 128 for t in res.tokens)
-            ref = res.tokens if ref is None else ref
+            ref.setdefault(pen, res.tokens)
             if a.slope:
-                eng.decode_pass(R, tail, None, 64, check_every=ce)
+                eng.decode_pass(R, tail, None, 64, check_every=ce, **hk)
                 torch.cuda.synchronize()
                 b64 = 1e9
                 for _ in range(a.reps):
                     t0 = time.perf_counter()
-                    eng.decode_pass(R, tail, None, 64, check_every=ce)
+                    eng.decode_pass(R, tail, None, 64, check_every=ce, **hk)
                     torch.cuda.synchronize()
                     b64 = min(b64, time.perf_counter() - t0)
-                print(json.dumps({"rows": R, "check_every": ce, "graph_steps": gs,
+                print(json.dumps({"rows": R, "check_every": ce, "graph_steps": gs, "penalties": pen,
                                   "pass64_ms": round(b64 * 1e3, 2),
                                   "slope_us_per_step": round((best - b64) * 1e6 / 64, 1),
                                   "fixed_ms": round((b64 - 66 * (best - b64) / 64) * 1e3, 2)}), flush=True)
-            print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs,
+            print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs, "penalties": pen,
                               "pass_ms": round(best * 1e3, 2),
-                              "step_us": round(best * 1e6 / 130, 1), "tokens_equal": res.tokens == ref}),
+                              "step_us": round(best * 1e6 / 130, 1), "tokens_equal": res.tokens == ref[pen]}),
                   flush=True)
+    if a.beams:
+        W, nb = a.beams
+        eng.row_map[:W] = torch.arange(W, dtype=torch.int32)
+        eng.seek[:W] = 0
+        eng.encode(W)
+        torch.cuda.synchronize()
+        for pen in a.penalties:
+            hk = {"repetition_penalty": 1.3, "no_repeat_ngram_size": 3} if pen else {}
+            eng.beam_pass(W, nb, tail, None, 128, **hk)  # warm-up: graph capture
+            torch.cuda.synchronize()
+            best = 1e9
+            for _ in range(a.reps):
+                t0 = time.perf_counter()
+                eng.beam_pass(W, nb, tail, None, 128, **hk)
+                torch.cuda.synchronize()
+                best = min(best, time.perf_counter() - t0)
+            print(json.dumps({"beam_windows": W, "num_beams": nb, "rows": W * nb, "penalties": pen,
+                              "pass_ms": round(best * 1e3, 2), "step_us": round(best * 1e6 / 130, 1)}), flush=True)
 
 
 if __name__ == "__main__":

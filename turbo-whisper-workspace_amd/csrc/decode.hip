@@ -551,6 +551,130 @@ extern "C" int tw_token_prob(const float* logits, int B, int ld_logits, int V, i
 }
 
 // =================================================================================================
+// History processors in front of the Whisper chain: RepetitionPenaltyLogitsProcessor
+// ($TF/generation/logits_process.py: gather, where(score < 0, score * p, score / p), scatter) then
+// NoRepeatNGramLogitsProcessor (_calc_banned_ngram_tokens: every token that followed an earlier occurrence of the
+// history's last n-1 tokens is set to -inf), in that order, as _get_logits_processor puts them before the
+// model-specific processors. One workgroup (1024 threads) per row, a thread per history position.
+//   history of row r = prefix[r][0 .. prefix_len[r]) ++ tokens[r][0 .. state[r][TW_ST_NGEN])
+//   (a prefix entry TW_HIST_LANG stands for the row's detected language, state[r][TW_ST_LANG]);
+//   to_logprobs: the row is first rewritten to log_softmax over [0, V) (beam search runs its processors on
+//   log-probabilities, $TF/generation/utils.py:3270-3275).
+// The penalty touches each distinct id once, from the value before any penalty (only the first occurrence's thread
+// reads and writes its id); a barrier separates it from the bans, so -inf wins. IEEE f32 multiply / divide (no
+// fast-math in this build): the values equal torch's f32 bit for bit. Finished rows and columns [V, ld) are left alone.
+// =================================================================================================
+#define TW_HIST_THREADS 1024
+#define TW_HIST_INFLIGHT 8  // logits of a thread's share loaded per trip (one load per trip serialised ~100 round trips)
+__global__ __launch_bounds__(TW_HIST_THREADS) void k_logits_history(float* __restrict__ logits, int ld_logits, int V,
+                                                                    const int* __restrict__ prefix, int ld_prefix,
+                                                                    const int* __restrict__ prefix_len,
+                                                                    const int* __restrict__ tokens, int ld_tokens,
+                                                                    const int* __restrict__ state, float penalty,
+                                                                    int ngram, int to_logprobs) {
+  TW_DEC_PRIO();
+  __shared__ int h[TW_HIST_MAX];
+  __shared__ float red[2 * (TW_HIST_THREADS / 64)];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int* st = state + r * TW_STATE_STRIDE;
+  if (st[TW_ST_FINISHED]) return;  // (uniform per block)
+  float* row = logits + (size_t)r * ld_logits;
+  const int pl = prefix ? min(max(prefix_len[r], 0), ld_prefix) : 0;
+  const int ng = min(max(st[TW_ST_NGEN], 0), ld_tokens);
+  const int L = min(pl + ng, TW_HIST_MAX);
+  for (int i = tid; i < L; i += TW_HIST_THREADS) {
+    int id = i < pl ? prefix[(size_t)r * ld_prefix + i] : tokens[(size_t)r * ld_tokens + (i - pl)];
+    if (id == TW_HIST_LANG) id = st[TW_ST_LANG];
+    h[i] = id;
+  }
+  if (to_logprobs) {
+    float m = -INFINITY, s = 0.f;
+    for (int base = tid; base < V; base += TW_HIST_INFLIGHT * TW_HIST_THREADS) {
+      float xs[TW_HIST_INFLIGHT];
+#pragma unroll
+      for (int u = 0; u < TW_HIST_INFLIGHT; ++u) {
+        const int v = base + u * TW_HIST_THREADS;
+        xs[u] = v < V ? row[v] : -INFINITY;
+      }
+#pragma unroll
+      for (int u = 0; u < TW_HIST_INFLIGHT; ++u) {  // online logsumexp, branch-free (as lse_add1, with expf)
+        const float x = xs[u], d = x - m;
+        const float e = (x == -INFINITY) ? 0.f : expf(-fabsf(d));
+        s = (d > 0.f) ? s * e + 1.f : s + e;
+        m = fmaxf(m, x);
+      }
+    }
+    auto merge = [](float& m, float& s, float m2, float s2) {
+      if (m2 == -INFINITY) return;
+      if (m == -INFINITY) { m = m2; s = s2; return; }
+      if (m2 > m) { s = s * expf(m - m2) + s2; m = m2; }
+      else s = s + s2 * expf(m2 - m);
+    };
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+    if ((tid & 63) == 0) {
+      red[2 * (tid >> 6)] = m;
+      red[2 * (tid >> 6) + 1] = s;
+    }
+    __syncthreads();
+    m = red[0];
+    s = red[1];
+    for (int w = 1; w < TW_HIST_THREADS / 64; ++w) merge(m, s, red[2 * w], red[2 * w + 1]);
+    const float lse = m + logf(s);
+    for (int base = tid; base < V; base += TW_HIST_INFLIGHT * TW_HIST_THREADS) {
+      float xs[TW_HIST_INFLIGHT];
+#pragma unroll
+      for (int u = 0; u < TW_HIST_INFLIGHT; ++u) {
+        const int v = base + u * TW_HIST_THREADS;
+        xs[u] = v < V ? row[v] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < TW_HIST_INFLIGHT; ++u) {
+        const int v = base + u * TW_HIST_THREADS;
+        if (v < V) row[v] = xs[u] - lse;
+      }
+    }
+  }
+  __syncthreads();  // h is staged; the row's log-probabilities are written
+  if (penalty != 1.0f) {
+    for (int i = tid; i < L; i += TW_HIST_THREADS) {
+      const int id = h[i];
+      if (id < 0 || id >= V) continue;
+      bool first = true;
+      for (int j = 0; j < i; ++j) first &= (h[j] != id);
+      if (!first) continue;
+      const float x = row[id];
+      row[id] = x < 0.f ? x * penalty : x / penalty;
+    }
+  }
+  __syncthreads();  // the bans come after every penalised value
+  if (ngram > 0 && L >= ngram) {
+    const int tail0 = L - ngram + 1;  // the history's last n-1 tokens start here
+    for (int i = tid; i <= L - ngram; i += TW_HIST_THREADS) {
+      bool match = true;
+      for (int k = 0; k < ngram - 1; ++k) match &= (h[i + k] == h[tail0 + k]);
+      const int id = h[i + ngram - 1];
+      if (match && id >= 0 && id < V) row[id] = -INFINITY;
+    }
+  }
+}
+
+extern "C" int tw_logits_history(float* logits, int R, int ld_logits, int V, const int* prefix, int ld_prefix,
+                                 const int* prefix_len, const int* tokens, int ld_tokens, const int* state,
+                                 float repetition_penalty, int no_repeat_ngram, int to_logprobs, void* stream) {
+  TW_REQUIRE(logits && tokens && state && R > 0, "tw_logits_history: bad args");
+  TW_REQUIRE(V > 0 && V <= ld_logits, "tw_logits_history: V=%d ld=%d", V, ld_logits);
+  TW_REQUIRE((prefix == nullptr) == (prefix_len == nullptr) && ld_prefix >= 0 && ld_tokens >= 0,
+             "tw_logits_history: prefix / prefix_len go together (ld_prefix=%d ld_tokens=%d)", ld_prefix, ld_tokens);
+  TW_REQUIRE(repetition_penalty > 0.f && repetition_penalty == repetition_penalty && no_repeat_ngram >= 0,
+             "tw_logits_history: repetition_penalty=%f no_repeat_ngram=%d", repetition_penalty, no_repeat_ngram);
+  hipLaunchKernelGGL(k_logits_history, dim3(R), dim3(TW_HIST_THREADS), 0, (hipStream_t)stream, logits, ld_logits, V,
+                     prefix, ld_prefix, prefix_len, tokens, ld_tokens, state, repetition_penalty, no_repeat_ngram,
+                     to_logprobs);
+  return tw_check_launch("tw_logits_history");
+}
+
+// =================================================================================================
 // Beam search (num_beams > 1): GenerationMixin._beam_search ($TF/generation/utils.py:3208-3512) with the same Whisper
 // processor chain, early_stopping=False, one EOS id. Rows are window-major: row = w * nb + j.
 //   k_beam_partial  grid (R, NC): per vocab chunk of a row, the log-sum-exp of the raw logits (log_softmax), the
@@ -932,7 +1056,9 @@ __global__ __launch_bounds__(512) void k_beam_step(const BeamPart<K>* __restrict
         } else {
           pick = top[1][bb++];
         }
-        rc[wid][k] = Cand{pick.v == -INFINITY ? -INFINITY : run + (pick.v - lse_all), pick.i};
+        // (bp.scores_are_logprobs: tw_logits_history already wrote log_softmax + the history processors)
+        const float lp_all = bp.scores_are_logprobs ? pick.v : pick.v - lse_all;
+        rc[wid][k] = Cand{pick.v == -INFINITY ? -INFINITY : run + lp_all, pick.i};
         if (lpt) rc_lp[wid][k] = pick.v == -INFINITY ? -INFINITY : run_lp + (pick.v - lse_ok);
       }
     }

@@ -314,6 +314,39 @@ void logits_select_(const Tensor& logits, const Tensor& suppress_bits, at::IntAr
      "logits_select");
 }
 
+// RepetitionPenaltyLogitsProcessor + NoRepeatNGramLogitsProcessor on the rows' history (prefix ++ generated tokens),
+// in place ahead of the selection ops (tw_logits_history); to_logprobs: log_softmax first (beam rows)
+void logits_history_(Tensor& logits, int64_t V, const c10::optional<Tensor>& prefix,
+                     const c10::optional<Tensor>& prefix_len, const Tensor& tokens, const Tensor& state,
+                     double repetition_penalty, int64_t no_repeat_ngram, bool to_logprobs) {
+  TW_OP_DEVICE(logits);
+  dev(logits, at::kFloat, "logits");
+  rows(logits, "logits");
+  const int64_t R = logits.size(0);
+  TORCH_CHECK(V > 0 && logits.size(1) >= V, "logits narrower than V");
+  TORCH_CHECK(repetition_penalty > 0.0 && no_repeat_ngram >= 0, "repetition_penalty > 0 and no_repeat_ngram >= 0");
+  dev(tokens, at::kInt, "tokens");
+  same_device(logits, tokens, "tokens");
+  rows(tokens, "tokens");
+  TORCH_CHECK(tokens.size(0) >= R, "tokens must hold R rows");
+  holds(logits, state, at::kInt, R * TW_STATE_STRIDE, "state");
+  const bool has_prefix = prefix.has_value() && prefix->defined();
+  TORCH_CHECK(has_prefix == (prefix_len.has_value() && prefix_len->defined()), "prefix and prefix_len go together");
+  if (has_prefix) {
+    dev(*prefix, at::kInt, "prefix");
+    same_device(logits, *prefix, "prefix");
+    rows(*prefix, "prefix");
+    TORCH_CHECK(prefix->size(0) >= R, "prefix must hold R rows");
+    holds(logits, *prefix_len, at::kInt, R, "prefix_len");
+  }
+  ok(tw_logits_history(ptr<float>(logits), (int)R, (int)logits.stride(0), (int)V,
+                       has_prefix ? ptr<int>(*prefix) : nullptr, has_prefix ? (int)prefix->stride(0) : 0,
+                       has_prefix ? ptr<int>(*prefix_len) : nullptr, ptr<int>(tokens), (int)tokens.stride(0),
+                       ptr<int>(state), (float)repetition_penalty, (int)no_repeat_ngram, to_logprobs ? 1 : 0,
+                       cur_stream(logits)),
+     "logits_history");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tw, m) {
@@ -337,6 +370,8 @@ TORCH_LIBRARY(tw, m) {
         "Tensor(a!) out) -> ()");
   m.def("logits_select_(Tensor logits, Tensor suppress_bits, int[] params, Tensor(a!) state, Tensor(b!)? tokens, "
         "Tensor(c!) ids, Tensor(d!) pos, Tensor(e!) workspace) -> ()");
+  m.def("logits_history_(Tensor(a!) logits, int V, Tensor? prefix, Tensor? prefix_len, Tensor tokens, Tensor state, "
+        "float repetition_penalty, int no_repeat_ngram, bool to_logprobs) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(tw, CUDA, m) {  // (the dispatch key of device tensors; on this ROCm build they are HIP tensors)
@@ -353,6 +388,7 @@ TORCH_LIBRARY_IMPL(tw, CUDA, m) {  // (the dispatch key of device tensors; on th
   m.impl("attn_decode_self_", &attn_decode_self_);
   m.impl("attn_decode_cross_out", &attn_decode_cross_out);
   m.impl("logits_select_", &logits_select_);
+  m.impl("logits_history_", &logits_history_);
 }
 
 TORCH_LIBRARY_IMPL(tw, Meta, m) {  // shape functions (FakeTensor / tracing); the out= and in-place ops write nothing
@@ -374,4 +410,6 @@ TORCH_LIBRARY_IMPL(tw, Meta, m) {  // shape functions (FakeTensor / tracing); th
                                      const Tensor&, Tensor&) {});
   m.impl("logits_select_", [](const Tensor&, const Tensor&, at::IntArrayRef, Tensor&, const c10::optional<Tensor>&,
                               Tensor&, Tensor&, Tensor&) {});
+  m.impl("logits_history_", [](Tensor&, int64_t, const c10::optional<Tensor>&, const c10::optional<Tensor>&,
+                               const Tensor&, const Tensor&, double, int64_t, bool) {});
 }

@@ -32,6 +32,8 @@ TW_SELECT_WS_PER_ROW = 128
 TW_STATE_STRIDE = 8
 TW_ST_NGEN, TW_ST_LAST, TW_ST_PENULT, TW_ST_LASTTS, TW_ST_FINISHED, TW_ST_LANG = 0, 1, 2, 3, 4, 5
 TW_ST_SUMLP, TW_ST_NOSPEECH = 6, 7  # f32 bits (tw_logits_sample / tw_token_prob)
+TW_HIST_MAX = 448   # tw_logits_history: ids per row history (prefix + generated)
+TW_HIST_LANG = -1   # a prefix entry that reads the detected language, state[r][TW_ST_LANG]
 
 # every symbol include/tw_whisper.h + include/tw_audio.h declare (tests check the .so exports all of them)
 EXPORTED = (
@@ -52,7 +54,7 @@ EXPORTED = (
     "tw_gemm_set_persistent_grid", "tw_mp3_probe", "tw_mp3_decode", "tw_aac_parse_asc", "tw_aac_decode_raw",
     "tw_aac_adts_probe", "tw_aac_adts_decode", "tw_dec_fused", "tw_dec_fused_sync_bytes", "tw_dec_fused_supported",
     "tw_dec_fused_set_grid", "tw_dec_fused_set_acquire", "tw_dec_fused_set_probe", "tw_dec_fused_grid",
-    "tw_dec_fused_xpart_bytes",
+    "tw_dec_fused_xpart_bytes", "tw_logits_history",
 )
 
 
@@ -67,7 +69,7 @@ class TwSelectParams(ctypes.Structure):
 
 class TwBeamParams(ctypes.Structure):
     _fields_ = [("num_beams", ctypes.c_int32), ("max_new", ctypes.c_int32), ("length_penalty", ctypes.c_float),
-                ("ld_tokens", ctypes.c_int32)]
+                ("ld_tokens", ctypes.c_int32), ("scores_are_logprobs", ctypes.c_int32)]
 
 
 class TwBeamState(ctypes.Structure):
@@ -163,6 +165,7 @@ _SIGS = {
     "tw_logits_sample": ([_P, _I, _I, _P, ctypes.POINTER(TwSelectParams), ctypes.c_float, _I, ctypes.c_uint64, _P, _P,
                           _P, _I, _P, _P, _P], _I),
     "tw_token_prob": ([_P, _I, _I, _I, _I, _P, _P], _I),
+    "tw_logits_history": ([_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _F, _I, _I, _P], _I),
     "tw_gemm_bf16_partial": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P], _I),
     "tw_gemv_set_wide_slices": ([_I], _I),
     "tw_gemv_set_variant": ([_I], _I),

@@ -302,6 +302,13 @@ class WhisperEngine:
         # prefix; while _masked, the self-attention masks those positions (tw_attn_decode_self_masked)
         self._kv_start = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)
         self._masked = False
+        # repetition_penalty / no_repeat_ngram_size (tw_logits_history ahead of every token selection): per row the
+        # decoder_input_ids its pass started from (prompt or previous segments with their left pads, SOT, language —
+        # TW_HIST_LANG where the pass detects it —, task, <|notimestamps|>) and their count; _hist = the current
+        # pass's (penalty, n-gram size), None when both are off (no launch, and the value every graph key carries)
+        self._hist_prefix = torch.zeros(self.max_rows, T, dtype=i32, device=dev)
+        self._hist_len = torch.zeros(self.max_rows, dtype=i32, device=dev)
+        self._hist: Optional[tuple] = None
         # the library's (tw_gemv_set_wide_slices, tw_gemv_set_variant) state (its defaults) and whether the decoder's
         # layers run as one persistent launch (tw_dec_fused) in the current pass
         self._dec_ctx = (1, 0, False)
@@ -904,6 +911,8 @@ class WhisperEngine:
                 self._select(min(VIEW_ROWS, R - r0), params, tokens, self._view(r0, min(VIEW_ROWS, R - r0)), embed_next)
             return
         v = v or self._view(0, R)
+        if params.mode == 0:  # (language detection sees the raw logits)
+            self._history(v.r0, R, v.stream)
         if embed_next:
             L0 = self.w.dec[0]
             _lib.call("tw_logits_select_embed", v.logits.data_ptr(), R, self.d.vocab, self.suppress_bits.data_ptr(),
@@ -916,6 +925,44 @@ class WhisperEngine:
         _lib.call("tw_logits_select", v.logits.data_ptr(), R, self.d.vocab, self.suppress_bits.data_ptr(),
                   ctypes.byref(params), v.state.data_ptr(), v.tokens.data_ptr() if tokens else None,
                   v.tokens.shape[1], v.ids.data_ptr(), v.pos.data_ptr(), v.sel_ws.data_ptr(), v.stream.cuda_stream)
+
+    def _hist_begin(self, R: int, repetition_penalty: float, no_repeat_ngram_size: int, tail: Sequence[int],
+                    lang_ids: Optional[Sequence[int]], prefix=None) -> None:
+        """Start a pass's token history for tw_logits_history: rows [0, R) of the prefix buffer take what
+        transformers hands its processors as decoder_input_ids before the first generated token — the pass's prefix
+        rows (prompt_ids / conditioned previous segments, left pads included), <|startoftranscript|>, the language
+        (TW_HIST_LANG when the pass detects it: the kernel reads state[r][TW_ST_LANG]) and the tail. With both
+        options off nothing is copied and no pre-pass is launched (_hist None)."""
+        p, n = float(repetition_penalty or 1.0), int(no_repeat_ngram_size or 0)
+        if p == 1.0 and n == 0:
+            self._hist = None
+            return
+        st = self.gen.special
+        rows = []
+        for r in range(R):
+            h = [int(t) for t in prefix[0][r]] if prefix is not None and prefix[0] else []
+            h.append(st.sot)
+            if st.is_multilingual:
+                h.append(_lib.TW_HIST_LANG if lang_ids is None else int(lang_ids[r]))
+            h.extend(int(t) for t in tail)
+            rows.append(h)
+        L = len(rows[0])
+        if L > self._hist_prefix.shape[1]:
+            raise ValueError(f"decoder prompt of {L} tokens exceeds {self._hist_prefix.shape[1]} positions")
+        self._hist_prefix[:R, :L] = torch.as_tensor(rows, dtype=torch.int32, device=self.device)
+        self._hist_len[:R] = L
+        self._hist = (p, n)
+
+    def _history(self, r0: int, R: int, stream, to_logprobs: bool = False) -> None:
+        """The history processors (repetition penalty, no-repeat n-gram) on the logits of rows [r0, r0 + R), in
+        place, when the pass set them (tw_logits_history; to_logprobs: beam rows, log_softmax first)."""
+        if self._hist is None:
+            return
+        p, n = self._hist
+        _lib.call("tw_logits_history", self.logits[r0:].data_ptr(), R, self.logits.stride(0), self.d.vocab,
+                  self._hist_prefix[r0:].data_ptr(), self._hist_prefix.stride(0), self._hist_len[r0:].data_ptr(),
+                  self.tokens[r0:].data_ptr(), self.tokens.stride(0), self.state[r0:].data_ptr(), p, n,
+                  int(to_logprobs), stream.cuda_stream)
 
     # Teacher-forcing hook of decode_pass (parity harness, tests/test_gpu_turbo.py and bench.py's parity leg):
     # hook(k, view) runs on the host after the step that produced generated position k (view None: the prompt's last
@@ -1104,17 +1151,22 @@ class WhisperEngine:
     @on_engine_streams
     def decode_pass(self, R: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]], max_new: int,
                     check_every: int = 8, use_timestamps: bool = True, align: bool = False,
-                    num_frames: Optional[Sequence[int]] = None, prefix=None) -> PassResult:
+                    num_frames: Optional[Sequence[int]] = None, prefix=None, repetition_penalty: float = 1.0,
+                    no_repeat_ngram_size: int = 0) -> PassResult:
         """Greedy decode of R rows from the prompt [SOT, (lang), *tail] (the init tokens of
         _retrieve_init_tokens; the language is detected from the SOT step when lang_ids is None on a
         multilingual model). Returns the generated tokens of every row; with align, also every row's token-level
         timestamps (alignment-head cross-attention of the fed tokens -> DTW; num_frames: the rows' valid frames
-        minus their seek, as generate() passes them)."""
+        minus their seek, as generate() passes them). repetition_penalty / no_repeat_ngram_size: generate()'s
+        RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor over prompt + generated tokens, ahead of every
+        selection (tw_logits_history)."""
         if align:
             P = self._prompt_len(tail, prefix)
             self._align_setup(R, P, max_new)
             try:
-                res = self.decode_pass(R, tail, lang_ids, max_new, check_every, use_timestamps, prefix=prefix)
+                res = self.decode_pass(R, tail, lang_ids, max_new, check_every, use_timestamps, prefix=prefix,
+                                       repetition_penalty=repetition_penalty,
+                                       no_repeat_ngram_size=no_repeat_ngram_size)
                 self._token_ts(R, P, res, num_frames)
                 return res
             finally:
@@ -1126,6 +1178,7 @@ class WhisperEngine:
         detect = st.is_multilingual and lang_ids is None
         params = self._select_params(0, max_new, use_timestamps)
         base = self._prefill(R, prefix)  # (condition_on_prev_tokens: the init tokens start at position base)
+        self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail, lang_ids, prefix)
 
         def prompt() -> None:
             """State reset, the prompt steps [SOT, (lang), *tail] and the first generated token (one token per
@@ -1157,7 +1210,8 @@ class WhisperEngine:
         if self.use_graphs and self.prompt_graph and (detect or not st.is_multilingual) and not base:
             al = self._align  # (keyed like _graph_for: an alignment pass captures the probability-recording kernel)
             key = ("prompt", R, tuple(int(t) for t in tail), max_new, use_timestamps, self._slot,
-                   None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()), self._dec_ctx)
+                   None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()), self._dec_ctx,
+                   self._hist)
             g = self._graphs.get(key)
             if g is None:
                 g = torch.cuda.CUDAGraph()
@@ -1260,20 +1314,24 @@ class WhisperEngine:
                     temperature: float = 0.0, top_k: int = 50, seed: int = 0, row_keys: Optional[Sequence[int]] = None,
                     use_timestamps: bool = True, enc_rows: Optional[Sequence[int]] = None, r_enc: Optional[int] = None,
                     no_speech_token: Optional[int] = None, check_every: int = 8, prefix=None, align: bool = False,
-                    num_frames: Optional[Sequence[int]] = None) -> PassResult:
+                    num_frames: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
+                    no_repeat_ngram_size: int = 0) -> PassResult:
         """One decode pass of the temperature-fallback loop (WhisperGenerationMixin.generate_with_fallback,
         generation_whisper.py:970-1116), eager, one tw_logits_sample per token: greedy when temperature == 0
         (the tokens of decode_pass), else a draw from softmax(processed / T) over the top_k scores. Per row it also
         returns the sum of the chosen tokens' log-probabilities (the avg_logprob criterion's numerator) and, with
         no_speech_token, WhisperNoSpeechDetection's probability of it at the SOT position. enc_rows: the encoder
         rows (of the r_enc-row encoded batch in this slot) the R decoder rows read (default 0..R-1). align: also the
-        rows' token-level timestamps (as decode_pass)."""
+        rows' token-level timestamps (as decode_pass). repetition_penalty / no_repeat_ngram_size as decode_pass: the
+        log-probability is then the penalised scores' (generate()'s output_scores)."""
         if align:
             P = self._prompt_len(tail, prefix)
             self._align_setup(R, P, max_new)
             try:
                 res = self.sample_pass(R, tail, lang_ids, max_new, temperature, top_k, seed, row_keys, use_timestamps,
-                                       enc_rows, r_enc, no_speech_token, check_every, prefix)
+                                       enc_rows, r_enc, no_speech_token, check_every, prefix,
+                                       repetition_penalty=repetition_penalty,
+                                       no_repeat_ngram_size=no_repeat_ngram_size)
                 self._token_ts(R, P, res, num_frames)
                 return res
             finally:
@@ -1295,6 +1353,7 @@ class WhisperEngine:
             self._row_group = 1
         try:
             base = self._prefill(R, prefix, r_enc)
+            self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail, lang_ids, prefix)
             self.state[:R].zero_()
             self.state[:R, _lib.TW_ST_LAST:_lib.TW_ST_LASTTS + 1] = -1
             self.pos[:R] = base
@@ -1327,6 +1386,7 @@ class WhisperEngine:
                 self.decoder_step(R, r_enc=r_enc)
                 if steps == 0 and not prompt_rest:
                     no_speech()
+                self._history(0, R, self.stream)
                 _lib.call("tw_logits_sample", self.logits.data_ptr(), R, V, self.suppress_bits.data_ptr(),
                           ctypes.byref(params), float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
                           keys.data_ptr(), self.state.data_ptr(), self.tokens.data_ptr(), self.tokens.shape[1],
@@ -1375,7 +1435,8 @@ class WhisperEngine:
                   use_timestamps: bool = True, check_every: int = 8, length_penalty: float = 1.0,
                   enc_row0: int = 0, r_enc: Optional[int] = None, prefix=None, align: bool = False,
                   num_frames: Optional[Sequence[int]] = None, enc_rows: Optional[Sequence[int]] = None,
-                  criteria: bool = False, no_speech_token: Optional[int] = None) -> PassResult:
+                  criteria: bool = False, no_speech_token: Optional[int] = None, repetition_penalty: float = 1.0,
+                  no_repeat_ngram_size: int = 0) -> PassResult:
         """Beam-search decode (GenerationMixin._beam_search, $TF/generation/utils.py:3208-3512) of W windows with
         num_beams rows each (row = w * num_beams + j, all reading window w's cross-K/V): the prompt as
         decode_pass (language detected from the SOT step when lang_ids is None), then per token one decoder step
@@ -1387,14 +1448,17 @@ class WhisperEngine:
         enc_rows: each window's encoder row (instead of enc_row0 + w: a fallback round's subset). criteria: also each
         best hypothesis' sum of log-probabilities renormalised over the allowed tokens (the fallback's average
         log-probability numerator, tw_beam_step's fin_lp) and, with no_speech_token, WhisperNoSpeechDetection's
-        probability at the <|startoftranscript|> step (PassResult.sum_logprob / no_speech_prob)."""
+        probability at the <|startoftranscript|> step (PassResult.sum_logprob / no_speech_prob).
+        repetition_penalty / no_repeat_ngram_size: the history processors on every beam's log-probabilities
+        (tw_logits_history with to_logprobs; tw_beam_step then takes the scores as they are)."""
         if align:
             P = self._prompt_len(tail, prefix)
             self._align_setup(W * num_beams, P, max_new)
             try:
                 res = self.beam_pass(W, num_beams, tail, lang_ids, max_new, use_timestamps, check_every, length_penalty,
                                      enc_row0, r_enc, prefix, enc_rows=enc_rows, criteria=criteria,
-                                     no_speech_token=no_speech_token)
+                                     no_speech_token=no_speech_token, repetition_penalty=repetition_penalty,
+                                     no_repeat_ngram_size=no_repeat_ngram_size)
                 bb = self._beam
                 nb, st = num_beams, self.gen.special
                 lens = [len(t) for t in res.tokens]  # generated tokens, EOS included (beam_indices' entries)
@@ -1442,6 +1506,10 @@ class WhisperEngine:
             base = self._prefill(R, None if prefix is None else
                                  ([prefix[0][w] for w in range(W) for _ in range(nb)],
                                   [prefix[1][w] for w in range(W) for _ in range(nb)]), r_enc)
+            # (a window's history prefix on each of its beam rows too)
+            self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail,
+                             None if lang_ids is None else [int(x) for x in lang_ids for _ in range(nb)],
+                             None if prefix is None else ([prefix[0][w] for w in range(W) for _ in range(nb)], None))
             self.state[:R].zero_()
             self.state[:R, _lib.TW_ST_LAST:_lib.TW_ST_LASTTS + 1] = -1
             self.pos[:R] = base
@@ -1484,7 +1552,7 @@ class WhisperEngine:
             bb["win"][:W] = torch.tensor([1, 0, 0, 0], dtype=torch.int32, device=dev)
             self.state[:R, _lib.TW_ST_NGEN] = 0
             sel = self._select_params(0, max_new, use_timestamps)
-            bp = _lib.TwBeamParams(nb, max_new, float(length_penalty), T)
+            bp = _lib.TwBeamParams(nb, max_new, float(length_penalty), T, int(self._hist is not None))
             bst = _lib.TwBeamState(bb["run_score"].data_ptr(), bb["fin_score"].data_ptr(), bb["fin_flag"].data_ptr(),
                                    bb["fin_len"].data_ptr(), bb["fin_tokens"].data_ptr(), bb["win"].data_ptr(),
                                    bb["src_rows"].data_ptr(), bb["kv_tab"].data_ptr(),
@@ -1495,6 +1563,7 @@ class WhisperEngine:
 
             def step() -> None:
                 self.decoder_step(R, r_enc=r_enc)
+                self._history(0, R, self.stream, to_logprobs=True)
                 _lib.call("tw_beam_step", self.logits.data_ptr(), W, self.d.vocab, self.suppress_bits.data_ptr(),
                           ctypes.byref(sel), ctypes.byref(bp), ctypes.byref(bst), self.state.data_ptr(),
                           self.tokens.data_ptr(), self.ids.data_ptr(), self.pos.data_ptr(), bb["ws"].data_ptr(), s)
@@ -1507,7 +1576,7 @@ class WhisperEngine:
                 al = self._align
                 key = ("beam", R, nb, max_new, bool(use_timestamps), float(length_penalty), self._slot, r_enc,
                        self._masked, None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()),
-                       bool(criteria), self._dec_ctx)
+                       bool(criteria), self._dec_ctx, self._hist)
                 g = self._graphs.get(key)
                 if g is None:
                     g = torch.cuda.CUDAGraph()
@@ -1520,6 +1589,7 @@ class WhisperEngine:
                     # (a bare <|startoftranscript|> prompt: its step is the first beam step, eager with the probability)
                     self.decoder_step(R, r_enc=r_enc)
                     no_speech()
+                    self._history(0, R, self.stream, to_logprobs=True)
                     _lib.call("tw_beam_step", self.logits.data_ptr(), W, V, self.suppress_bits.data_ptr(),
                               ctypes.byref(sel), ctypes.byref(bp), ctypes.byref(bst), self.state.data_ptr(),
                               self.tokens.data_ptr(), self.ids.data_ptr(), self.pos.data_ptr(), bb["ws"].data_ptr(), s)
@@ -1565,7 +1635,7 @@ class WhisperEngine:
         al = self._align
         key = (R, params.max_new, params.use_timestamps, self._slot, i, fused,
                None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()), self._masked, self._dec_ctx,
-               n_steps)
+               n_steps, self._hist)
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -1615,7 +1685,8 @@ class WhisperEngine:
                  num_frames: Optional[Sequence[int]] = None, fallback: Optional[FallbackConfig] = None,
                  window_offset: int = 0, condition_on_prev_tokens: bool = False,
                  prompt_ids: Optional[Sequence[int]] = None,
-                 prompt_condition_type: Optional[str] = None) -> List[List[int]]:
+                 prompt_condition_type: Optional[str] = None, repetition_penalty: float = 1.0,
+                 no_repeat_ngram_size: int = 0, length_penalty: float = 1.0) -> List[List[int]]:
         """Whisper short-form generate() over feats[slot][:n_chunks] (each 3000 frames): language
         detection, the seek loop and segment extraction, returning for every chunk the concatenated
         segment tokens (what generate() returns before padding).
@@ -1632,7 +1703,9 @@ class WhisperEngine:
         every pass is prompted with it (:1909-1912); conditioned, "first-segment" makes it the chunks' first segment
         (:1119-1124: behind <|startofprev|>, cut with the rest to the last 223 tokens) and "all-segments" puts it in
         front of the previous segments of every pass after the first (:1887-1888). The language is detected from the
-        SOT step alone, before any prompt (detect_language); the prompt is not part of the returned tokens."""
+        SOT step alone, before any prompt (detect_language); the prompt is not part of the returned tokens.
+        repetition_penalty / no_repeat_ngram_size: generate()'s history processors on every pass (each seek pass
+        starts a new history: its prompt + what it generated); length_penalty: beam search's exponent."""
         if slot is not None:
             self.use_slot(slot)
         if pre_encoded and n_chunks > self.max_batch:
@@ -1686,14 +1759,18 @@ class WhisperEngine:
             return self._seek_loop(n_chunks, tail, prompt_len, max_new_tokens, max_new, seek, segs, passes_raw, langs,
                                    tts, maxf, seg_lists, do_cond, prev_sot, condition_on_prev_tokens, max_passes,
                                    pre_encoded, num_beams, word_timestamps, num_frames, fb, return_timestamps,
-                                   window_offset, prompt)
+                                   window_offset, prompt,
+                                   hist={"repetition_penalty": float(repetition_penalty or 1.0),
+                                         "no_repeat_ngram_size": int(no_repeat_ngram_size or 0)},
+                                   length_penalty=float(1.0 if length_penalty is None else length_penalty))
         finally:
             self._masked = False
 
     def _seek_loop(self, n_chunks, tail, prompt_len, max_new_tokens, max_new, seek, segs, passes_raw, langs, tts, maxf,
                    seg_lists, do_cond, prev_sot, condition, max_passes, pre_encoded, num_beams, word_timestamps,
-                   num_frames, fb, return_timestamps, window_offset, prompt=None):
+                   num_frames, fb, return_timestamps, window_offset, prompt=None, hist=None, length_penalty=1.0):
         st = self.gen.special
+        hist = hist or {}
         passes = 0
         while any(seek[i] < maxf[i] for i in range(n_chunks)):
             rows = [i for i in range(n_chunks) if seek[i] < maxf[i]]
@@ -1742,7 +1819,7 @@ class WhisperEngine:
                     toks_f, skip_f, lang_f, temp_f, nb_left, ts_f = self._fallback_pass(
                         R, tail, given, mnew, return_timestamps, fb, [window_offset + i for i in part], passes,
                         enc_row0=b0 if pre else 0, r_enc=n_chunks if pre else R, prefix=pfx, num_beams=num_beams,
-                        align=word_timestamps, num_frames=nf_part)
+                        align=word_timestamps, num_frames=nf_part, hist=hist, length_penalty=length_penalty)
                     num_beams = nb_left  # (a sampling round left generation_config.num_beams = 1)
                     for j in range(R):  # (by position in the pass's batch, as transformers writes it)
                         do_cond[j] = bool(condition) and (temp_f[j] is None or temp_f[j] < 0.5)
@@ -1765,10 +1842,11 @@ class WhisperEngine:
                     pre = pre_encoded and passes == 0
                     res = self.beam_pass(R, num_beams, tail, given, mnew, use_timestamps=return_timestamps,
                                          enc_row0=b0 if pre else 0, r_enc=n_chunks if pre else R, prefix=pfx,
-                                         align=word_timestamps, num_frames=nf_part)
+                                         align=word_timestamps, num_frames=nf_part, length_penalty=length_penalty,
+                                         **hist)
                 else:
                     res = self.decode_pass(R, tail, given, mnew, use_timestamps=return_timestamps,
-                                           align=word_timestamps, num_frames=nf_part, prefix=pfx)
+                                           align=word_timestamps, num_frames=nf_part, prefix=pfx, **hist)
                 self._masked = False
                 for j in range(R):
                     do_cond[j] = bool(condition)
@@ -1804,7 +1882,8 @@ class WhisperEngine:
     def _fallback_pass(self, R: int, tail, given, max_new: int, return_timestamps: bool, fb: FallbackConfig,
                        windows: Sequence[int], pass_no: int, enc_row0: int = 0, r_enc: Optional[int] = None,
                        prefix=None, num_beams: int = 1, align: bool = False,
-                       num_frames: Optional[Sequence[int]] = None):
+                       num_frames: Optional[Sequence[int]] = None, hist: Optional[dict] = None,
+                       length_penalty: float = 1.0):
         """generate_with_fallback (generation_whisper.py:970-1116) for one seek pass of R encoded rows: decode at
         the first temperature, re-decode the rows whose criteria fail at the next one, until none does or the
         temperatures run out. Returns per row the kept sequence (EOS removed), should_skip, the language ids, each
@@ -1839,14 +1918,15 @@ class WhisperEngine:
             if nb > 1:
                 res = self.beam_pass(len(idx), nb, tail, sub_lang, max_new, use_timestamps=return_timestamps,
                                      enc_rows=[enc_row0 + i for i in idx], r_enc=r_enc, prefix=sub_pfx,
-                                     criteria=True, no_speech_token=ns_tok, align=align, num_frames=sub_nf)
+                                     criteria=True, no_speech_token=ns_tok, align=align, num_frames=sub_nf,
+                                     length_penalty=length_penalty, **(hist or {}))
             else:
                 res = self.sample_pass(len(idx), tail, sub_lang, max_new,
                                        temperature=float(t) if do_sample else 0.0, top_k=fb.top_k, seed=fb.seed,
                                        row_keys=[fallback_row_key(windows[i], pass_no, fi) for i in idx],
                                        use_timestamps=return_timestamps, enc_rows=[enc_row0 + i for i in idx],
                                        r_enc=r_enc, no_speech_token=ns_tok, prefix=sub_pfx, align=align,
-                                       num_frames=sub_nf)
+                                       num_frames=sub_nf, **(hist or {}))
             self._masked = False
             if align:
                 for j, i in enumerate(idx):

@@ -167,6 +167,7 @@ class TurboTranscriber:
         if "prompt_ids" not in prompt:
             prompt = {}
         fallback = self._fallback_config(gk)
+        hist = self._history_options(gk)
         if gk:
             raise ValueError(f"generate_kwargs not supported by this engine: {sorted(gk)}")
         st = self.gen.special
@@ -197,7 +198,7 @@ class TurboTranscriber:
             return self._long_form(wav, task=task, language=language, return_timestamps=return_timestamps,
                                    return_language=return_language, max_new_tokens=max_new_tokens,
                                    num_beams=num_beams, max_passes=max_passes, fallback=fallback, condition=cond,
-                                   prompt=prompt)
+                                   prompt=prompt, history=hist)
         else:
             windows = [Window(0, len(wav), 0, 0, True)]
             with_stride = False
@@ -214,6 +215,7 @@ class TurboTranscriber:
                       **({"fallback": fallback, "window_base": base} if fallback.active else {}),
                       **({"condition_on_prev_tokens": True} if cond else {}),
                       **({"prompt": prompt} if prompt else {}),
+                      **({"history": hist} if hist else {}),
                       **({"group": batch_size} if grouped else {}))
             if word:  # token times ride along as floats after the tokens (one all-gather carries both)
                 nf = [-(-min(x.length, CHUNK_SAMPLES) // 160) for x in ws]
@@ -254,7 +256,7 @@ class TurboTranscriber:
         return lt[tok]
 
     def _long_form(self, wav, *, task, language, return_timestamps, return_language, max_new_tokens, num_beams,
-                   max_passes, fallback, condition=False, prompt=None) -> dict:
+                   max_passes, fallback, condition=False, prompt=None, history=None) -> dict:
         """An input longer than 30 s without chunk_length_s: the pipeline hands generate() the features of the whole
         input (feature extractor with truncation=False, padding="longest", $TF/pipelines/automatic_speech_recognition
         .py:450-457) and generate() runs its seek loop over all of them (generation_whisper.py:647-968: is_shortform
@@ -270,6 +272,7 @@ class TurboTranscriber:
         try:
             kw = {"fallback": fallback} if fallback.active else {}
             kw.update(prompt or {})
+            kw.update(history or {})
             if word:  # num_frames: the feature extractor's attention mask, one per hop (_set_num_frames)
                 kw.update(word_timestamps=True, num_frames=[-(-int(x.shape[0]) // 160)])
             toks = eng.generate(1, task=task, lang_ids=None if lang_id is None else [lang_id],
@@ -295,7 +298,7 @@ class TurboTranscriber:
                            num_frames: Optional[Sequence[int]] = None, group: Optional[int] = None,
                            max_passes: Optional[int] = None, fallback: Optional[FallbackConfig] = None,
                            window_base: int = 0, condition_on_prev_tokens: bool = False,
-                           prompt: Optional[dict] = None) -> List[List[int]]:
+                           prompt: Optional[dict] = None, history: Optional[dict] = None) -> List[List[int]]:
         """Log-mel + generate for every window; returns per-window token sequences (generate() output,
         right-padded with the pad token within each engine batch, as the HF batch output is). Batches of
         max_batch windows go through WhisperEngine.run_batches: batch k+1 is encoded while batch k decodes.
@@ -306,6 +309,9 @@ class TurboTranscriber:
         `batch_size` (its DataLoader batch, $TF/pipelines/base.py:1319-1339) is honoured there; segment-level
         tokens are per-window results, so batching is then only a schedule: the windows are cut into near-equal
         batches of at most max_batch (and into two when sub_batch_min says so).
+
+        history: generate()'s repetition_penalty / no_repeat_ngram_size / length_penalty (those that are set), handed
+        to every batch's generate(): per-pass token histories, so the results stay per-window.
 
         wav: a host array, or a torch tensor (a rank's copy of the broadcast waveform, in device memory)."""
         eng = self.engine
@@ -346,7 +352,7 @@ class TurboTranscriber:
                               max_passes=max_passes,
                               **({"fallback": fallback, "window_offset": window_base} if fallback is not None else {}),
                               **({"condition_on_prev_tokens": True} if condition_on_prev_tokens else {}),
-                              **(prompt or {}))
+                              **(prompt or {}), **(history or {}))
         out: List[List[int]] = []
         for seqs in res:
             out.extend(pad_right(seqs, self.gen.special.eot))
@@ -356,6 +362,28 @@ class TurboTranscriber:
         self.last_window_prefixes = [p for bp in eng.batch_prefixes for p in bp]
         if word_timestamps:  # per window the concatenated segments' token times (not padded, as the pipeline's)
             self.last_window_token_timestamps = [t for bt in eng.batch_token_timestamps for t in bt]
+        return out
+
+    @staticmethod
+    def _history_options(gk: Dict[str, Any]) -> Dict[str, Any]:
+        """Pops generate()'s `repetition_penalty`, `no_repeat_ngram_size` and `length_penalty`; returns those that
+        are on as WhisperEngine.generate's kwargs (None, 1.0 and 0 mean off, as _get_logits_processor reads them).
+        Values are checked as RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor check them
+        (generation/logits_process.py), with their messages."""
+        out: Dict[str, Any] = {}
+        p = gk.pop("repetition_penalty", None)
+        if p is not None and p != 1.0:
+            if not isinstance(p, float) or not (p > 0):
+                raise ValueError(f"`penalty` has to be a strictly positive float, but is {p}")
+            out["repetition_penalty"] = p
+        n = gk.pop("no_repeat_ngram_size", None)
+        if n:  # (None and 0 are off, as generate() reads them)
+            if not isinstance(n, int) or n <= 0:
+                raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {n}")
+            out["no_repeat_ngram_size"] = int(n)
+        lp = gk.pop("length_penalty", None)
+        if lp is not None and float(lp) != 1.0:
+            out["length_penalty"] = float(lp)
         return out
 
     def _fallback_config(self, gk: Dict[str, Any]) -> FallbackConfig:
