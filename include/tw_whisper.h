@@ -231,6 +231,9 @@ typedef struct TwBeamState {
                           * renormalised over the allowed tokens (log_softmax of the processed beam scores:
                           * _retrieve_avg_logprobs, generation_whisper.py:1958-1975); initialise 0                  */
   float* fin_lp;         /* f32[R] or NULL: the same sum of each finished slot's hypothesis                       */
+  float* run_tlp;        /* f32[R][ld_tokens] or NULL (with fin_tlp; needs run_lp / fin_lp): the terms of run_lp, one
+                          * per generated position of each running beam (moved with the token histories)             */
+  float* fin_tlp;        /* f32[R][ld_tokens] or NULL: the terms of fin_lp, positions [0, fin_len) of each slot      */
 } TwBeamState;
 /* workspace: tw_beam_workspace_bytes(R) bytes of device memory. */
 size_t tw_beam_workspace_bytes(int rows);
@@ -449,6 +452,19 @@ int tw_logits_select_embed(const float* logits, int B, int ld_logits, const uint
 int tw_logits_sample(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
                      const TwSelectParams* params, float temperature, int top_k, uint64_t seed, const int* row_key,
                      int* state, int* tokens_out, int ld_tokens, int* next_ids, int* pos, void* stream);
+/* tw_logits_sample that also writes the step's term: token_lp f32[B][ld_lp] (NULL: exactly tw_logits_sample) gets,
+ * at the position n_gen the step writes, log_softmax(scores)[token] — the value added to TW_ST_SUMLP — or 0.0 for a
+ * pad written after the row finished. Tokens, draws and state are tw_logits_sample's. */
+int tw_logits_sample_lp(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
+                        const TwSelectParams* params, float temperature, int top_k, uint64_t seed, const int* row_key,
+                        int* state, int* tokens_out, int ld_tokens, int* next_ids, int* pos, float* token_lp,
+                        int ld_lp, void* stream);
+/* Per-token log-probability of the greedy path, launched in front of tw_logits_select / tw_logits_select_embed on
+ * the same logits, params and (still unchanged) state: lp_out[b][n_gen] = log_softmax(processed scores)[token the
+ * selection is about to commit] (tw_logits_sample's temperature-0 term, from the same scan), 0.0 for a finished row.
+ * One workgroup per row; the state is only read. */
+int tw_token_logprob(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
+                     const TwSelectParams* params, const int* state, float* lp_out, int ld_lp, void* stream);
 /* state[b][TW_ST_NOSPEECH] (f32 bits) = softmax(logits[b][0:V])[token]: WhisperNoSpeechDetection's no_speech_prob
  * ($TF/generation/logits_process.py:2050-2112) from the logits at the <|startoftranscript|> position. */
 int tw_token_prob(const float* logits, int B, int ld_logits, int V, int token, int* state, void* stream);

@@ -4,12 +4,15 @@ detection, task token) + 128 generated tokens with EOS suppressed, i.e. 130 deco
 before, untimed. Prints one JSON line per (rows, mode).
 
     python scripts/decode_step_time.py [--rows 15 24 64] [--reps 3] [--fused 0 1] [--penalties 0 1] [--beams 12 5]
+                                       [--logprobs 0 1]
 
 --fused 1: the decoder's layers as one persistent launch (tw_dec_fused) at every row count <= 32, 0: the launch chain
 (WhisperEngine.dec_fused_alone / dec_fused_max_rows overridden); with both, each row count runs both and reports
 whether their tokens agree.
 --penalties 1: the passes run with repetition_penalty=1.3 and no_repeat_ngram_size=3 (tw_logits_history queued ahead
 of every selection), 0: without; with both, the cost of the pre-pass is the difference of the two lines.
+--logprobs 1: the passes run with token_logprobs (tw_token_logprob captured ahead of every selection; the beam pass
+with run_tlp / fin_tlp), 0: without; with both, the cost of the pre-kernel is the difference of the two lines.
 --beams W NB: also the beam pass of W windows x NB beams (one captured step per token: decoder step over W * NB rows,
 tw_beam_step), 128 tokens with EOS suppressed, per step from the pass's wall time.
 """
@@ -40,6 +43,7 @@ def main():
                     "pass's fixed costs")
     ap.add_argument("--penalties", type=int, nargs="+", default=[0])
     ap.add_argument("--beams", type=int, nargs=2, default=None, metavar=("W", "NB"))
+    ap.add_argument("--logprobs", type=int, nargs="+", default=[0])
     a = ap.parse_args()
     dims = PRESETS["large-v3-turbo"]
     gen = GenerationSettings.default(dims)
@@ -56,8 +60,8 @@ def main():
         eng.encode(R)
         torch.cuda.synchronize()
         ref = {}  # per penalties value: the first mode's tokens
-        for fz, ce, gs, pen in [(f, c, g, p) for f in a.fused for c in a.check_every for g in a.graph_steps
-                                for p in a.penalties]:
+        for fz, ce, gs, pen, lpo in [(f, c, g, p, q) for f in a.fused for c in a.check_every for g in a.graph_steps
+                                     for p in a.penalties for q in a.logprobs]:
             if fz and R > 32:
                 continue
             eng.dec_fused_alone = bool(fz)
@@ -65,6 +69,8 @@ def main():
             eng.graph_steps_alone = gs
             eng._graphs.clear()
             hk = {"repetition_penalty": 1.3, "no_repeat_ngram_size": 3} if pen else {}
+            if lpo:
+                hk["token_logprobs"] = True
             eng.decode_pass(R, tail, None, 128, check_every=ce, **hk)  # warm-up: graph captures
             torch.cuda.synchronize()
             best = 1e9
@@ -77,7 +83,7 @@ def main():
             loop_us = min(e0.elapsed_time(e1) * 1e3 / n for e0, e1, n, _ in eng.pass_events)
             eng.pass_events = None
             print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs, "penalties": pen,
-                              "loop_us_per_step": round(loop_us, 1)}),
+                              "logprobs": lpo, "loop_us_per_step": round(loop_us, 1)}),
                   flush=True)
             assert all(len(t) == 128 for t in res.tokens)
             ref.setdefault(pen, res.tokens)
@@ -95,7 +101,7 @@ def main():
                                   "slope_us_per_step": round((best - b64) * 1e6 / 64, 1),
                                   "fixed_ms": round((b64 - 66 * (best - b64) / 64) * 1e3, 2)}), flush=True)
             print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs, "penalties": pen,
-                              "pass_ms": round(best * 1e3, 2),
+                              "logprobs": lpo, "pass_ms": round(best * 1e3, 2),
                               "step_us": round(best * 1e6 / 130, 1), "tokens_equal": res.tokens == ref[pen]}),
                   flush=True)
     if a.beams:
@@ -104,8 +110,10 @@ def main():
         eng.seek[:W] = 0
         eng.encode(W)
         torch.cuda.synchronize()
-        for pen in a.penalties:
+        for pen, lpo in [(p, q) for p in a.penalties for q in a.logprobs]:
             hk = {"repetition_penalty": 1.3, "no_repeat_ngram_size": 3} if pen else {}
+            if lpo:
+                hk["token_logprobs"] = True
             eng.beam_pass(W, nb, tail, None, 128, **hk)  # warm-up: graph capture
             torch.cuda.synchronize()
             best = 1e9
@@ -114,7 +122,7 @@ def main():
                 eng.beam_pass(W, nb, tail, None, 128, **hk)
                 torch.cuda.synchronize()
                 best = min(best, time.perf_counter() - t0)
-            print(json.dumps({"beam_windows": W, "num_beams": nb, "rows": W * nb, "penalties": pen,
+            print(json.dumps({"beam_windows": W, "num_beams": nb, "rows": W * nb, "penalties": pen, "logprobs": lpo,
                               "pass_ms": round(best * 1e3, 2), "step_us": round(best * 1e6 / 130, 1)}), flush=True)
 
 

@@ -413,7 +413,8 @@ __global__ __launch_bounds__(256) void k_select_full(const float* __restrict__ l
                                                      float temperature, int top_k, uint64_t seed,
                                                      const int* __restrict__ row_key, int* __restrict__ state,
                                                      int* __restrict__ tokens_out, int ld_tokens,
-                                                     int* __restrict__ next_ids, int* __restrict__ pos) {
+                                                     int* __restrict__ next_ids, int* __restrict__ pos,
+                                                     float* __restrict__ token_lp, int ld_lp) {
   __shared__ SelPart sp[4];
   __shared__ SelPart parts[TW_SELECT_CHUNKS];
   __shared__ float red[8];
@@ -510,11 +511,57 @@ __global__ __launch_bounds__(256) void k_select_full(const float* __restrict__ l
   if (tid != 0) return;
   if (pos) pos[b] += 1;
   const int was_finished = st[TW_ST_FINISHED];
+  const int q = st[TW_ST_NGEN];  // the position this step writes
   const int tok = sel_commit(p, st, sel, tokens_out, ld_tokens, next_ids, b);
+  float lp = 0.f;  // (a pad after the row finished)
   if (!was_finished) {
-    const float lp = row[tok] - lse;
+    lp = row[tok] - lse;
     st[TW_ST_SUMLP] = __float_as_int(__int_as_float(st[TW_ST_SUMLP]) + lp);
   }
+  if (token_lp && q >= 0 && q < ld_lp) token_lp[(size_t)b * ld_lp + q] = lp;
+}
+
+// grid B, 256 threads (mode 0), in front of tw_logits_select / _select_embed: the log-probability of the token that
+// selection is about to commit, under the step's processed scores — k_select_full's temperature <= 0 branch (the same
+// sel_chunk<true> scan, merge, rule and greedy choice on the same inputs, so the same token and the term TW_ST_SUMLP
+// sums) without the commit: the row state is only read.
+__global__ TW_DEC_LB(256, 1) void k_token_logprob(const float* __restrict__ logits, int ld_logits,
+                                                  const uint32_t* __restrict__ suppress_bits, TwSelectParams p,
+                                                  const int* __restrict__ state, float* __restrict__ lp_out,
+                                                  int ld_lp) {
+  TW_DEC_PRIO();
+  __shared__ SelPart sp[4];
+  __shared__ SelPart parts[TW_SELECT_CHUNKS];
+  __shared__ float red[8];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int* st = state + b * TW_STATE_STRIDE;
+  const int q = st[TW_ST_NGEN];
+  if (q < 0 || q >= ld_lp) return;  // (uniform per block)
+  if (st[TW_ST_FINISHED]) {
+    if (tid == 0) lp_out[(size_t)b * ld_lp + q] = 0.f;
+    return;
+  }
+  const RowMask rm = row_mask(st, p);
+  const float* row = logits + (size_t)b * ld_logits;
+  const int V = p.V, NC = TW_SELECT_CHUNKS;
+  float m_tx = -INFINITY, s_tx = 0.f;
+  for (int c = 0; c < NC; ++c) {
+    SelPart out;
+    sel_chunk<true>(row, suppress_bits, p, rm, (int)((long)c * V / NC), (int)((long)(c + 1) * V / NC), sp, out, m_tx,
+                    s_tx);
+    if (tid == 0) parts[c] = out;
+    __syncthreads();
+  }
+  block_lse256(m_tx, s_tx, red);
+  Best bt, bs;
+  float m_ts, s_ts;
+  sel_merge(parts, NC, 0, lane, bt, bs, m_ts, s_ts);
+  if (tid != 0) return;
+  const bool fire = sel_rule_fires(p, bt, m_ts, s_ts);
+  const int sel = sel_greedy(p, bt, bs, m_ts, s_ts);
+  float m = fire ? -INFINITY : m_tx, sm = fire ? 0.f : s_tx;
+  if (p.use_timestamps) lse_merge(m, sm, m_ts, s_ts);
+  lp_out[(size_t)b * ld_lp + q] = row[sel] - (m + __logf(sm));
 }
 
 // grid B, 256 threads: softmax(raw logits)[token] into the state slot TW_ST_NOSPEECH (f32 bits)
@@ -529,18 +576,40 @@ __global__ __launch_bounds__(256) void k_token_prob(const float* __restrict__ lo
     state[blockIdx.x * TW_STATE_STRIDE + TW_ST_NOSPEECH] = __float_as_int(__expf(row[token] - (m + __logf(s))));
 }
 
-extern "C" int tw_logits_sample(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
-                                const TwSelectParams* params, float temperature, int top_k, uint64_t seed,
-                                const int* row_key, int* state, int* tokens_out, int ld_tokens, int* next_ids,
-                                int* pos, void* stream) {
+extern "C" int tw_logits_sample_lp(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
+                                   const TwSelectParams* params, float temperature, int top_k, uint64_t seed,
+                                   const int* row_key, int* state, int* tokens_out, int ld_tokens, int* next_ids,
+                                   int* pos, float* token_lp, int ld_lp, void* stream) {
   TW_REQUIRE(logits && params && state && B > 0, "tw_logits_sample: bad args");
   TW_REQUIRE(params->mode == 0, "tw_logits_sample: generation steps (mode 0) only");
   TW_REQUIRE(params->V > 0 && params->V <= ld_logits, "tw_logits_sample: V=%d ld=%d", params->V, ld_logits);
   TW_REQUIRE(params->n_begin_suppress >= 0 && params->n_begin_suppress <= 8, "tw_logits_sample: begin_suppress");
   TW_REQUIRE(temperature >= 0.f && temperature == temperature, "tw_logits_sample: temperature %f", temperature);
+  TW_REQUIRE(!token_lp || ld_lp > 0, "tw_logits_sample_lp: ld_lp=%d", ld_lp);
   hipLaunchKernelGGL(k_select_full, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ld_logits, suppress_bits,
-                     *params, temperature, top_k, seed, row_key, state, tokens_out, ld_tokens, next_ids, pos);
+                     *params, temperature, top_k, seed, row_key, state, tokens_out, ld_tokens, next_ids, pos,
+                     token_lp, ld_lp);
   return tw_check_launch("tw_logits_sample");
+}
+
+extern "C" int tw_logits_sample(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
+                                const TwSelectParams* params, float temperature, int top_k, uint64_t seed,
+                                const int* row_key, int* state, int* tokens_out, int ld_tokens, int* next_ids,
+                                int* pos, void* stream) {
+  return tw_logits_sample_lp(logits, B, ld_logits, suppress_bits, params, temperature, top_k, seed, row_key, state,
+                             tokens_out, ld_tokens, next_ids, pos, nullptr, 0, stream);
+}
+
+extern "C" int tw_token_logprob(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
+                                const TwSelectParams* params, const int* state, float* lp_out, int ld_lp,
+                                void* stream) {
+  TW_REQUIRE(logits && params && state && lp_out && B > 0 && ld_lp > 0, "tw_token_logprob: bad args");
+  TW_REQUIRE(params->mode == 0, "tw_token_logprob: generation steps (mode 0) only");
+  TW_REQUIRE(params->V > 0 && params->V <= ld_logits, "tw_token_logprob: V=%d ld=%d", params->V, ld_logits);
+  TW_REQUIRE(params->n_begin_suppress >= 0 && params->n_begin_suppress <= 8, "tw_token_logprob: begin_suppress");
+  hipLaunchKernelGGL(k_token_logprob, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ld_logits, suppress_bits,
+                     *params, state, lp_out, ld_lp);
+  return tw_check_launch("tw_token_logprob");
 }
 
 extern "C" int tw_token_prob(const float* logits, int B, int ld_logits, int V, int token, int* state, void* stream) {
@@ -941,6 +1010,8 @@ __global__ __launch_bounds__(512) void k_beam_step(const BeamPart<K>* __restrict
   // (bs.run_lp: every candidate's running sum of log-probabilities renormalised over the allowed tokens — what
   // _retrieve_avg_logprobs takes from the processed beam scores — carried beside the beam scores)
   __shared__ float rc_lp[TW_BEAM_MAXNB][K], c_lp[2 * K], s_lp[TW_BEAM_MAXNB], f_lp[TW_BEAM_MAXNB];
+  // (bs.run_tlp / fin_tlp: each candidate's own term of that sum, written at position t of the per-token histories)
+  __shared__ float rc_tm[TW_BEAM_MAXNB][K], c_tm[2 * K], s_tm[TW_BEAM_MAXNB];
   __shared__ int c_beam[2 * K], c_tok[2 * K];
   // per-row sorted lists and the one-thread bookkeeping arrays live in LDS: as per-thread arrays with runtime
   // indices they were lowered to scratch (224-768 B/lane) and the serial section ran at scratch latency
@@ -950,6 +1021,7 @@ __global__ __launch_bounds__(512) void k_beam_step(const BeamPart<K>* __restrict
   const int w = blockIdx.x, nb = bp.num_beams, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int ldt = bp.ld_tokens;
   const bool lpt = bs.run_lp != nullptr && bs.fin_lp != nullptr;
+  const bool tlp = lpt && bs.run_tlp != nullptr && bs.fin_tlp != nullptr;
   int* win = bs.win + 4 * w;
   const int t = win[2];
   const float NEG = -1.0e9f;
@@ -958,6 +1030,9 @@ __global__ __launch_bounds__(512) void k_beam_step(const BeamPart<K>* __restrict
   // length are staged too (any value: they are never read back)
   constexpr int STG = (TW_BEAM_MAXNB * TW_BEAM_MAXT + 511) / 512;
   int rt[STG], rf[STG], rk[STG], rft[STG];
+  // the per-token log-probability histories stay in registers (no LDS left for two more staged arrays): every thread
+  // reads its entries here, before any block-wide barrier, and in section 3 writes them to the slots that take them
+  float rl[STG], rfl[STG];
   const bool tab = bs.kv_tab != nullptr;
   const bool ftab = tab && bs.fin_tab != nullptr;
 #pragma unroll
@@ -969,6 +1044,8 @@ __global__ __launch_bounds__(512) void k_beam_step(const BeamPart<K>* __restrict
     rf[u] = ok ? bs.fin_tokens[off] : 0;
     rk[u] = ok && tab ? bs.kv_tab[off] : 0;
     rft[u] = ok && ftab ? bs.fin_tab[off] : 0;
+    rl[u] = ok && tlp ? bs.run_tlp[off] : 0.f;
+    rfl[u] = ok && tlp ? bs.fin_tlp[off] : 0.f;
   }
   const int st_v = tid < nb * TW_STATE_STRIDE ? state[(w * nb) * TW_STATE_STRIDE + tid] : 0;
   const int fl_v = tid < nb ? bs.fin_len[w * nb + tid] : 0;
@@ -1060,6 +1137,7 @@ __global__ __launch_bounds__(512) void k_beam_step(const BeamPart<K>* __restrict
         const float lp_all = bp.scores_are_logprobs ? pick.v : pick.v - lse_all;
         rc[wid][k] = Cand{pick.v == -INFINITY ? -INFINITY : run + lp_all, pick.i};
         if (lpt) rc_lp[wid][k] = pick.v == -INFINITY ? -INFINITY : run_lp + (pick.v - lse_ok);
+        if (tlp) rc_tm[wid][k] = pick.v == -INFINITY ? -INFINITY : pick.v - lse_ok;
       }
     }
   }
@@ -1105,6 +1183,7 @@ __global__ __launch_bounds__(512) void k_beam_step(const BeamPart<K>* __restrict
       c_tok[rank] = rc[j][k].i;
       csc[rank] = v;
       if (lpt) c_lp[rank] = rc_lp[j][k];
+      if (tlp) c_tm[rank] = rc_tm[j][k];
     }
   }
   __syncthreads();
@@ -1141,6 +1220,7 @@ __global__ __launch_bounds__(512) void k_beam_step(const BeamPart<K>* __restrict
       s_tok[rank] = c_tok[c];
       s_score[rank] = rsc[c];
       if (lpt) s_lp[rank] = c_lp[c];
+      if (tlp) s_tm[rank] = c_tm[c];
     }
   }
   // f. finished beams: best nb of the nb + K merged scores (ties -> lower e)
@@ -1210,6 +1290,31 @@ __global__ __launch_bounds__(512) void k_beam_step(const BeamPart<K>* __restrict
         r = q <= old_pos[src] ? old_tab[src][q] : 0;
       }
       bs.fin_tab[(size_t)(w * nb + qs) * ldt + q] = r;
+    }
+  }
+  // the per-token log-probabilities move as tokens / fin_tokens do: positions [0, t) of a source's history (held in
+  // this thread's registers since the kernel's start) go to every slot that continues or keeps it, position t takes
+  // the continuation's own term
+  if (tlp) {
+#pragma unroll
+    for (int u = 0; u < STG; ++u) {
+      const int e = tid + 512 * u, j = e / TW_BEAM_MAXT, q = e % TW_BEAM_MAXT;
+      if (j >= nb || q >= ldt) continue;
+      for (int d = 0; d < nb; ++d) {
+        const size_t off = (size_t)(w * nb + d) * ldt + q;
+        if (s_src[d] == j && q < t) bs.run_tlp[off] = rl[u];
+        const int from = f_from[d];
+        if (from < nb) {
+          if (from == j && q < old_flen[j]) bs.fin_tlp[off] = rfl[u];
+        } else if (c_beam[from - nb] == j && q < t) {
+          bs.fin_tlp[off] = rl[u];
+        }
+      }
+    }
+    if (tid < nb && t < ldt) {
+      const size_t off = (size_t)(w * nb + tid) * ldt + t;
+      bs.run_tlp[off] = s_tm[tid];
+      if (f_from[tid] >= nb) bs.fin_tlp[off] = c_tm[f_from[tid] - nb];
     }
   }
   if (tid < nb) {

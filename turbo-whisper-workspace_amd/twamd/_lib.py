@@ -54,7 +54,7 @@ EXPORTED = (
     "tw_gemm_set_persistent_grid", "tw_mp3_probe", "tw_mp3_decode", "tw_aac_parse_asc", "tw_aac_decode_raw",
     "tw_aac_adts_probe", "tw_aac_adts_decode", "tw_dec_fused", "tw_dec_fused_sync_bytes", "tw_dec_fused_supported",
     "tw_dec_fused_set_grid", "tw_dec_fused_set_acquire", "tw_dec_fused_set_probe", "tw_dec_fused_grid",
-    "tw_dec_fused_xpart_bytes", "tw_logits_history",
+    "tw_dec_fused_xpart_bytes", "tw_logits_history", "tw_token_logprob", "tw_logits_sample_lp",
 )
 
 
@@ -76,7 +76,8 @@ class TwBeamState(ctypes.Structure):
     _fields_ = [("run_score", ctypes.c_void_p), ("fin_score", ctypes.c_void_p), ("fin_flag", ctypes.c_void_p),
                 ("fin_len", ctypes.c_void_p), ("fin_tokens", ctypes.c_void_p), ("win", ctypes.c_void_p),
                 ("src_rows", ctypes.c_void_p), ("kv_tab", ctypes.c_void_p), ("fin_tab", ctypes.c_void_p),
-                ("run_lp", ctypes.c_void_p), ("fin_lp", ctypes.c_void_p)]
+                ("run_lp", ctypes.c_void_p), ("fin_lp", ctypes.c_void_p),
+                ("run_tlp", ctypes.c_void_p), ("fin_tlp", ctypes.c_void_p)]
 
 
 class TwFlacInfo(ctypes.Structure):
@@ -164,6 +165,9 @@ _SIGS = {
     "tw_logits_select": ([_P, _I, _I, _P, ctypes.POINTER(TwSelectParams), _P, _P, _I, _P, _P, _P, _P], _I),
     "tw_logits_sample": ([_P, _I, _I, _P, ctypes.POINTER(TwSelectParams), ctypes.c_float, _I, ctypes.c_uint64, _P, _P,
                           _P, _I, _P, _P, _P], _I),
+    "tw_logits_sample_lp": ([_P, _I, _I, _P, ctypes.POINTER(TwSelectParams), ctypes.c_float, _I, ctypes.c_uint64, _P,
+                             _P, _P, _I, _P, _P, _P, _I, _P], _I),
+    "tw_token_logprob": ([_P, _I, _I, _P, ctypes.POINTER(TwSelectParams), _P, _P, _I, _P], _I),
     "tw_token_prob": ([_P, _I, _I, _I, _I, _P, _P], _I),
     "tw_logits_history": ([_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _F, _I, _I, _P], _I),
     "tw_gemm_bf16_partial": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P], _I),

@@ -176,23 +176,28 @@ def transcribe_sharded(run_windows, wav: np.ndarray, windows: Sequence, device: 
                        group=None, timed: bool = False, force_collective: Optional[bool] = None) -> List:
     """Every rank calls this with the same `windows` (chunk_iter windows over `wav`); each rank runs
     `run_windows(wav, windows[lo:hi]) -> List[List[int]]` on its own shard, then the results are all-gathered
-    into the global window order. `timed`: run_windows returns (tokens, per-token times) pairs (word
-    timestamps); the times are gathered too and the pairs are returned."""
+    into the global window order. `timed`: run_windows returns tuples (tokens, per-token floats, ...) with that
+    many float lanes after the tokens (True = 1: word timestamps' times; 2 with return_confidence's
+    log-probabilities behind them); every lane is gathered too and the tuples are returned."""
     rank, ws = world()
     lo, hi = shard_range(len(windows), ws, rank)
     err: Optional[BaseException] = None
     toks: List = []
     bits: List = []
+    lanes = int(timed)
     try:
         local = run_windows(wav, list(windows[lo:hi])) if hi > lo else []
         if len(local) != hi - lo:
             raise ValueError(f"rank {rank}: {len(local)} results for {hi - lo} windows")
         # (inside the try: a malformed result must reach agree() too, ADVICE r2)
-        toks = [list(t) for t, _ in local] if timed else [list(t) for t in local]
-        bits = [np.asarray(ts, dtype=np.float32).view(np.int32).tolist() for _, ts in local] if timed else []
+        toks = [list(x[0]) for x in local] if timed else [list(t) for t in local]
+        if timed and any(len(x) != 1 + lanes for x in local):
+            raise ValueError(f"rank {rank}: results without {lanes} float lanes")
+        bits = [[np.asarray(x[1 + k], dtype=np.float32).view(np.int32).tolist() for x in local] for k in range(lanes)]
     except Exception as e:  # made collective below: every rank learns of it before anyone enters the gather
         err, toks, bits = e, [], []
-    failed, width = agree(err is not None, max((len(t) for t in list(toks) + bits), default=0), device, group)
+    failed, width = agree(err is not None, max((len(t) for t in list(toks) + [b for ln in bits for b in ln]),
+                                               default=0), device, group)
     if failed:
         if err is not None:
             raise err
@@ -201,10 +206,13 @@ def transcribe_sharded(run_windows, wav: np.ndarray, windows: Sequence, device: 
                             force_collective=force_collective)
     if not timed:
         return seqs
-    # word timestamps: (tokens, per-token float32 times); the times travel as their int32 bit patterns
-    tsb, _ = gather_tokens(bits, None, len(windows), device=device, group=group, width=width,
-                           force_collective=force_collective)
-    return [(s, np.asarray(b, dtype=np.int32).view(np.float32).tolist()) for s, b in zip(seqs, tsb)]
+    # (tokens, per-token float32 lanes); the floats travel as their int32 bit patterns
+    out = [(s,) for s in seqs]
+    for k in range(lanes):
+        tsb, _ = gather_tokens(bits[k] if k < len(bits) else [], None, len(windows), device=device, group=group,
+                               width=width, force_collective=force_collective)
+        out = [o + (np.asarray(b, dtype=np.int32).view(np.float32).tolist(),) for o, b in zip(out, tsb)]
+    return out
 
 
 # ---- sharded _decode_asr -------------------------------------------------------------------------------------------
@@ -232,7 +240,7 @@ def _language_of(vocab, tokens) -> Optional[str]:
     return None
 
 
-def assumed_state(vocab, outputs: Sequence[dict], lo: int) -> dict:
+def assumed_state(vocab, outputs: Sequence[dict], lo: int, confidence: bool = False) -> dict:
     """The incoming state a shard starting at window `lo` assumes: clean, last language and time offset exact."""
     from .tokenizer import AsrStitcher
     lang = None
@@ -246,13 +254,13 @@ def assumed_state(vocab, outputs: Sequence[dict], lo: int) -> dict:
             chunk_len, stride_left, stride_right = o["stride"]
             t -= stride_left
             t += chunk_len - stride_right
-    return AsrStitcher.initial_state(lang, t)
+    return AsrStitcher.initial_state(lang, t, confidence=confidence)
 
 
 def shard_piece(vocab, outputs: Sequence[dict], lo: int, hi: int, **kw) -> tuple:
     """One shard's stitching: (assumed incoming state, its closed chunks, its final state)."""
     from .tokenizer import AsrStitcher
-    st0 = assumed_state(vocab, outputs, lo)
+    st0 = assumed_state(vocab, outputs, lo, bool(kw.get("confidence", False)))
     sti = AsrStitcher(vocab, state=st0, **kw)
     for o in outputs[lo:hi]:
         sti.feed(o)
@@ -264,7 +272,7 @@ def merge_pieces(vocab, outputs: Sequence[dict], pieces: Sequence[tuple], bounds
     """The serial _decode_asr result from the shards' pieces (see above); returns (text, optional)."""
     from .tokenizer import AsrStitcher
     chunks: List[dict] = []
-    true = AsrStitcher.initial_state()
+    true = AsrStitcher.initial_state(confidence=bool(kw.get("confidence", False)))
     restitched = 0
     for (assumed, ch, final), (lo, hi) in zip(pieces, bounds):
         if assumed == true:
@@ -291,7 +299,7 @@ def stitch_sharded(vocab, outputs: Sequence[dict], group=None, force_collective:
     """decode_asr over every window (`outputs` in global order, identical on every rank), with the work split over
     the ranks: each stitches its own window shard, one all_gather_object brings the pieces to every rank, and every
     rank merges them (merge_pieces). kw: decode_asr's return_timestamps, return_language, time_precision,
-    segment_size."""
+    segment_size, confidence."""
     from .tokenizer import decode_asr
     rank, ws = world()
     # without timestamps no window closes its chunk (the text accumulates until the end), so every shard after the

@@ -191,6 +191,9 @@ class PassResult:
     token_ts: Optional[List[np.ndarray]] = None  # per row, token-level times (prompt zeros first; word timestamps)
     sum_logprob: Optional[List[float]] = None  # per row, sum of the chosen tokens' log-probs (sample_pass)
     no_speech_prob: Optional[List[float]] = None  # per row, softmax at the SOT position of <|nospeech|> (sample_pass)
+    # per row, one float per generated token: log_softmax(the step's processed scores)[token] (token_logprobs), the
+    # terms sum_logprob sums; 0.0 for a pad after the row finished
+    token_lp: Optional[List[List[float]]] = None
 
 
 class WhisperEngine:
@@ -288,6 +291,10 @@ class WhisperEngine:
         self.sel_ws = torch.empty(B, _lib.TW_SELECT_WS_PER_ROW, dtype=f32, device=dev)
         self.state = torch.zeros(B, _lib.TW_STATE_STRIDE, dtype=i32, device=dev)
         self.tokens = torch.zeros(B, T, dtype=i32, device=dev)
+        # token_logprobs: the generated tokens' log-probabilities (tw_token_logprob / tw_logits_sample_lp / tw_beam_step);
+        # _tlp: the pass in progress asked for them (part of the captured graphs' keys)
+        self.token_lp = torch.zeros(B, T, dtype=f32, device=dev)
+        self._tlp = False
         self.ids = torch.zeros(B, dtype=i32, device=dev)
         self.pos = torch.zeros(B, dtype=i32, device=dev)
         self.row_map = torch.zeros(max_batch, dtype=i32, device=dev)
@@ -913,6 +920,10 @@ class WhisperEngine:
         v = v or self._view(0, R)
         if params.mode == 0:  # (language detection sees the raw logits)
             self._history(v.r0, R, v.stream)
+            if self._tlp:  # the log-probability of the token the selection below commits (state still unchanged)
+                _lib.call("tw_token_logprob", v.logits.data_ptr(), R, self.d.vocab, self.suppress_bits.data_ptr(),
+                          ctypes.byref(params), v.state.data_ptr(), self.token_lp[v.r0:].data_ptr(),
+                          self.token_lp.stride(0), v.stream.cuda_stream)
         if embed_next:
             L0 = self.w.dec[0]
             _lib.call("tw_logits_select_embed", v.logits.data_ptr(), R, self.d.vocab, self.suppress_bits.data_ptr(),
@@ -1152,25 +1163,37 @@ class WhisperEngine:
     def decode_pass(self, R: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]], max_new: int,
                     check_every: int = 8, use_timestamps: bool = True, align: bool = False,
                     num_frames: Optional[Sequence[int]] = None, prefix=None, repetition_penalty: float = 1.0,
-                    no_repeat_ngram_size: int = 0) -> PassResult:
+                    no_repeat_ngram_size: int = 0, token_logprobs: bool = False) -> PassResult:
         """Greedy decode of R rows from the prompt [SOT, (lang), *tail] (the init tokens of
         _retrieve_init_tokens; the language is detected from the SOT step when lang_ids is None on a
         multilingual model). Returns the generated tokens of every row; with align, also every row's token-level
         timestamps (alignment-head cross-attention of the fed tokens -> DTW; num_frames: the rows' valid frames
         minus their seek, as generate() passes them). repetition_penalty / no_repeat_ngram_size: generate()'s
         RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor over prompt + generated tokens, ahead of every
-        selection (tw_logits_history)."""
+        selection (tw_logits_history). token_logprobs: also every generated token's log-probability under the step's
+        processed scores (PassResult.token_lp), from tw_token_logprob in front of every selection."""
         if align:
             P = self._prompt_len(tail, prefix)
             self._align_setup(R, P, max_new)
             try:
                 res = self.decode_pass(R, tail, lang_ids, max_new, check_every, use_timestamps, prefix=prefix,
                                        repetition_penalty=repetition_penalty,
-                                       no_repeat_ngram_size=no_repeat_ngram_size)
+                                       no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs)
                 self._token_ts(R, P, res, num_frames)
                 return res
             finally:
                 self._align = None
+        if token_logprobs:
+            self._tlp = True
+            try:
+                res = self.decode_pass(R, tail, lang_ids, max_new, check_every, use_timestamps, prefix=prefix,
+                                       repetition_penalty=repetition_penalty,
+                                       no_repeat_ngram_size=no_repeat_ngram_size)
+            finally:
+                self._tlp = False
+            lp = self.token_lp[:R].tolist()
+            res.token_lp = [lp[r][: len(res.tokens[r])] for r in range(R)]
+            return res
         st = self.gen.special
         dev = self.device
         self._dec_context()
@@ -1211,7 +1234,7 @@ class WhisperEngine:
             al = self._align  # (keyed like _graph_for: an alignment pass captures the probability-recording kernel)
             key = ("prompt", R, tuple(int(t) for t in tail), max_new, use_timestamps, self._slot,
                    None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()), self._dec_ctx,
-                   self._hist)
+                   self._hist, self._tlp)
             g = self._graphs.get(key)
             if g is None:
                 g = torch.cuda.CUDAGraph()
@@ -1315,7 +1338,7 @@ class WhisperEngine:
                     use_timestamps: bool = True, enc_rows: Optional[Sequence[int]] = None, r_enc: Optional[int] = None,
                     no_speech_token: Optional[int] = None, check_every: int = 8, prefix=None, align: bool = False,
                     num_frames: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
-                    no_repeat_ngram_size: int = 0) -> PassResult:
+                    no_repeat_ngram_size: int = 0, token_logprobs: bool = False) -> PassResult:
         """One decode pass of the temperature-fallback loop (WhisperGenerationMixin.generate_with_fallback,
         generation_whisper.py:970-1116), eager, one tw_logits_sample per token: greedy when temperature == 0
         (the tokens of decode_pass), else a draw from softmax(processed / T) over the top_k scores. Per row it also
@@ -1323,7 +1346,8 @@ class WhisperEngine:
         no_speech_token, WhisperNoSpeechDetection's probability of it at the SOT position. enc_rows: the encoder
         rows (of the r_enc-row encoded batch in this slot) the R decoder rows read (default 0..R-1). align: also the
         rows' token-level timestamps (as decode_pass). repetition_penalty / no_repeat_ngram_size as decode_pass: the
-        log-probability is then the penalised scores' (generate()'s output_scores)."""
+        log-probability is then the penalised scores' (generate()'s output_scores). token_logprobs: also the terms of
+        that sum, one per generated token (PassResult.token_lp, tw_logits_sample_lp)."""
         if align:
             P = self._prompt_len(tail, prefix)
             self._align_setup(R, P, max_new)
@@ -1331,7 +1355,7 @@ class WhisperEngine:
                 res = self.sample_pass(R, tail, lang_ids, max_new, temperature, top_k, seed, row_keys, use_timestamps,
                                        enc_rows, r_enc, no_speech_token, check_every, prefix,
                                        repetition_penalty=repetition_penalty,
-                                       no_repeat_ngram_size=no_repeat_ngram_size)
+                                       no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs)
                 self._token_ts(R, P, res, num_frames)
                 return res
             finally:
@@ -1387,10 +1411,17 @@ class WhisperEngine:
                 if steps == 0 and not prompt_rest:
                     no_speech()
                 self._history(0, R, self.stream)
-                _lib.call("tw_logits_sample", self.logits.data_ptr(), R, V, self.suppress_bits.data_ptr(),
-                          ctypes.byref(params), float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                          keys.data_ptr(), self.state.data_ptr(), self.tokens.data_ptr(), self.tokens.shape[1],
-                          self.ids.data_ptr(), self.pos.data_ptr(), s)
+                if token_logprobs:
+                    _lib.call("tw_logits_sample_lp", self.logits.data_ptr(), R, V, self.suppress_bits.data_ptr(),
+                              ctypes.byref(params), float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                              keys.data_ptr(), self.state.data_ptr(), self.tokens.data_ptr(), self.tokens.shape[1],
+                              self.ids.data_ptr(), self.pos.data_ptr(), self.token_lp.data_ptr(),
+                              self.token_lp.stride(0), s)
+                else:
+                    _lib.call("tw_logits_sample", self.logits.data_ptr(), R, V, self.suppress_bits.data_ptr(),
+                              ctypes.byref(params), float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                              keys.data_ptr(), self.state.data_ptr(), self.tokens.data_ptr(), self.tokens.shape[1],
+                              self.ids.data_ptr(), self.pos.data_ptr(), s)
                 steps += 1
                 if steps % check_every == 0 and bool(self.state[:R, _lib.TW_ST_FINISHED].all().item()):
                     break
@@ -1403,10 +1434,12 @@ class WhisperEngine:
         if self._dec_ctx[2]:
             self.check_fused()
         f32 = stt.view(torch.float32)
+        lp = self.token_lp[:R].tolist() if token_logprobs else None
         return PassResult([toks[r][: ngen[r]] for r in range(R)],
                           stt[:, _lib.TW_ST_LANG].tolist() if detect else list(lang_ids) if lang_ids is not None else None,
                           sum_logprob=f32[:, _lib.TW_ST_SUMLP].tolist(),
-                          no_speech_prob=f32[:, _lib.TW_ST_NOSPEECH].tolist() if no_speech_token is not None else None)
+                          no_speech_prob=f32[:, _lib.TW_ST_NOSPEECH].tolist() if no_speech_token is not None else None,
+                          token_lp=None if lp is None else [lp[r][: ngen[r]] for r in range(R)])
 
     def _beam_buffers(self, R: int) -> dict:
         if self._beam is None or self._beam["rows"] < R:
@@ -1427,6 +1460,7 @@ class WhisperEngine:
                 "fin_tab": torch.zeros(self.max_rows, T, dtype=torch.int32, device=dev),
                 "run_lp": torch.zeros(self.max_rows, dtype=torch.float32, device=dev),
                 "fin_lp": torch.zeros(self.max_rows, dtype=torch.float32, device=dev),
+                "fin_tlp": torch.zeros(self.max_rows, T, dtype=torch.float32, device=dev),
             }
         return self._beam
 
@@ -1436,7 +1470,7 @@ class WhisperEngine:
                   enc_row0: int = 0, r_enc: Optional[int] = None, prefix=None, align: bool = False,
                   num_frames: Optional[Sequence[int]] = None, enc_rows: Optional[Sequence[int]] = None,
                   criteria: bool = False, no_speech_token: Optional[int] = None, repetition_penalty: float = 1.0,
-                  no_repeat_ngram_size: int = 0) -> PassResult:
+                  no_repeat_ngram_size: int = 0, token_logprobs: bool = False) -> PassResult:
         """Beam-search decode (GenerationMixin._beam_search, $TF/generation/utils.py:3208-3512) of W windows with
         num_beams rows each (row = w * num_beams + j, all reading window w's cross-K/V): the prompt as
         decode_pass (language detected from the SOT step when lang_ids is None), then per token one decoder step
@@ -1450,7 +1484,8 @@ class WhisperEngine:
         log-probability numerator, tw_beam_step's fin_lp) and, with no_speech_token, WhisperNoSpeechDetection's
         probability at the <|startoftranscript|> step (PassResult.sum_logprob / no_speech_prob).
         repetition_penalty / no_repeat_ngram_size: the history processors on every beam's log-probabilities
-        (tw_logits_history with to_logprobs; tw_beam_step then takes the scores as they are)."""
+        (tw_logits_history with to_logprobs; tw_beam_step then takes the scores as they are). token_logprobs: also the
+        terms of the best hypothesis' renormalised sum, one per token (PassResult.token_lp, tw_beam_step's fin_tlp)."""
         if align:
             P = self._prompt_len(tail, prefix)
             self._align_setup(W * num_beams, P, max_new)
@@ -1458,7 +1493,7 @@ class WhisperEngine:
                 res = self.beam_pass(W, num_beams, tail, lang_ids, max_new, use_timestamps, check_every, length_penalty,
                                      enc_row0, r_enc, prefix, enc_rows=enc_rows, criteria=criteria,
                                      no_speech_token=no_speech_token, repetition_penalty=repetition_penalty,
-                                     no_repeat_ngram_size=no_repeat_ngram_size)
+                                     no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs)
                 bb = self._beam
                 nb, st = num_beams, self.gen.special
                 lens = [len(t) for t in res.tokens]  # generated tokens, EOS included (beam_indices' entries)
@@ -1546,7 +1581,8 @@ class WhisperEngine:
             bb["fin_score"][:R] = -1e9
             bb["fin_flag"][:R] = 0
             bb["fin_len"][:R] = 0
-            if criteria:
+            lps = criteria or token_logprobs  # (the per-token terms ride on the renormalised sums)
+            if lps:
                 bb["run_lp"][:R] = 0.0
                 bb["fin_lp"][:R] = 0.0
             bb["win"][:W] = torch.tensor([1, 0, 0, 0], dtype=torch.int32, device=dev)
@@ -1557,8 +1593,10 @@ class WhisperEngine:
                                    bb["fin_len"].data_ptr(), bb["fin_tokens"].data_ptr(), bb["win"].data_ptr(),
                                    bb["src_rows"].data_ptr(), bb["kv_tab"].data_ptr(),
                                    bb["fin_tab"].data_ptr() if self._align is not None else None,
-                                   bb["run_lp"].data_ptr() if criteria else None,
-                                   bb["fin_lp"].data_ptr() if criteria else None)
+                                   bb["run_lp"].data_ptr() if lps else None,
+                                   bb["fin_lp"].data_ptr() if lps else None,
+                                   self.token_lp.data_ptr() if token_logprobs else None,  # (run_tlp: beside tokens)
+                                   bb["fin_tlp"].data_ptr() if token_logprobs else None)
             s = self.stream.cuda_stream
 
             def step() -> None:
@@ -1576,7 +1614,7 @@ class WhisperEngine:
                 al = self._align
                 key = ("beam", R, nb, max_new, bool(use_timestamps), float(length_penalty), self._slot, r_enc,
                        self._masked, None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()),
-                       bool(criteria), self._dec_ctx, self._hist)
+                       bool(criteria), self._dec_ctx, self._hist, bool(token_logprobs))
                 g = self._graphs.get(key)
                 if g is None:
                     g = torch.cuda.CUDAGraph()
@@ -1604,6 +1642,7 @@ class WhisperEngine:
             flen = bb["fin_len"][:R:nb].tolist()
             ftok = bb["fin_tokens"][:R:nb].tolist()
             sum_lp = bb["fin_lp"][:R:nb].tolist() if criteria else None
+            flp = bb["fin_tlp"][:R:nb].tolist() if token_logprobs else None
             nsp = (self.state[:R:nb, _lib.TW_ST_NOSPEECH].contiguous().view(torch.float32).tolist()
                    if no_speech_token is not None else None)
         finally:
@@ -1611,7 +1650,8 @@ class WhisperEngine:
             self._row_group = 1
             self._kv_tab = None
         return PassResult([ftok[w][: flen[w]] for w in range(W)], detected if lang_ids is None else list(lang_ids),
-                          sum_logprob=sum_lp, no_speech_prob=nsp)
+                          sum_logprob=sum_lp, no_speech_prob=nsp,
+                          token_lp=None if flp is None else [flp[w][: flen[w]] for w in range(W)])
 
     def _chains(self, R: int) -> List[DecView]:
         """Contiguous row ranges of [0, R), one per decode chain (each with its own partial-sum buffer)."""
@@ -1635,7 +1675,7 @@ class WhisperEngine:
         al = self._align
         key = (R, params.max_new, params.use_timestamps, self._slot, i, fused,
                None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()), self._masked, self._dec_ctx,
-               n_steps, self._hist)
+               n_steps, self._hist, self._tlp)
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -1686,7 +1726,8 @@ class WhisperEngine:
                  window_offset: int = 0, condition_on_prev_tokens: bool = False,
                  prompt_ids: Optional[Sequence[int]] = None,
                  prompt_condition_type: Optional[str] = None, repetition_penalty: float = 1.0,
-                 no_repeat_ngram_size: int = 0, length_penalty: float = 1.0) -> List[List[int]]:
+                 no_repeat_ngram_size: int = 0, length_penalty: float = 1.0,
+                 token_logprobs: bool = False) -> List[List[int]]:
         """Whisper short-form generate() over feats[slot][:n_chunks] (each 3000 frames): language
         detection, the seek loop and segment extraction, returning for every chunk the concatenated
         segment tokens (what generate() returns before padding).
@@ -1705,7 +1746,11 @@ class WhisperEngine:
         front of the previous segments of every pass after the first (:1887-1888). The language is detected from the
         SOT step alone, before any prompt (detect_language); the prompt is not part of the returned tokens.
         repetition_penalty / no_repeat_ngram_size: generate()'s history processors on every pass (each seek pass
-        starts a new history: its prompt + what it generated); length_penalty: beam search's exponent."""
+        starts a new history: its prompt + what it generated); length_penalty: beam search's exponent.
+        token_logprobs: every pass also records each generated token's log-probability under the step's processed
+        scores (output_scores: after the history and Whisper processors and the warpers, at temperature 1 — the terms
+        of _retrieve_avg_logprobs): last_pass_logprobs parallel to last_passes, last_token_logprobs parallel to the
+        returned segment tokens (else both None). Tokens are those of the same call without it."""
         if slot is not None:
             self.use_slot(slot)
         if pre_encoded and n_chunks > self.max_batch:
@@ -1762,16 +1807,22 @@ class WhisperEngine:
                                    window_offset, prompt,
                                    hist={"repetition_penalty": float(repetition_penalty or 1.0),
                                          "no_repeat_ngram_size": int(no_repeat_ngram_size or 0)},
-                                   length_penalty=float(1.0 if length_penalty is None else length_penalty))
+                                   length_penalty=float(1.0 if length_penalty is None else length_penalty),
+                                   token_logprobs=bool(token_logprobs))
         finally:
             self._masked = False
 
     def _seek_loop(self, n_chunks, tail, prompt_len, max_new_tokens, max_new, seek, segs, passes_raw, langs, tts, maxf,
                    seg_lists, do_cond, prev_sot, condition, max_passes, pre_encoded, num_beams, word_timestamps,
-                   num_frames, fb, return_timestamps, window_offset, prompt=None, hist=None, length_penalty=1.0):
+                   num_frames, fb, return_timestamps, window_offset, prompt=None, hist=None, length_penalty=1.0,
+                   token_logprobs=False):
         st = self.gen.special
         hist = hist or {}
         passes = 0
+        # token_logprobs: per chunk the kept tokens' log-probabilities (beside segs) and every pass's (beside passes_raw)
+        tlps: List[List[float]] = [[] for _ in range(n_chunks)]
+        passes_lp: List[List[List[float]]] = [[] for _ in range(n_chunks)]
+        lpkw = {"token_logprobs": True} if token_logprobs else {}
         while any(seek[i] < maxf[i] for i in range(n_chunks)):
             rows = [i for i in range(n_chunks) if seek[i] < maxf[i]]
             per = self.max_batch if num_beams == 1 else min(self.max_batch, self.max_rows // num_beams)
@@ -1816,10 +1867,11 @@ class WhisperEngine:
                 nf_part = None if num_frames is None else [int(num_frames[i]) - seek[i] for i in part]
                 if fb is not None:
                     pre = pre_encoded and passes == 0
-                    toks_f, skip_f, lang_f, temp_f, nb_left, ts_f = self._fallback_pass(
+                    toks_f, skip_f, lang_f, temp_f, nb_left, ts_f, lp_f = self._fallback_pass(
                         R, tail, given, mnew, return_timestamps, fb, [window_offset + i for i in part], passes,
                         enc_row0=b0 if pre else 0, r_enc=n_chunks if pre else R, prefix=pfx, num_beams=num_beams,
-                        align=word_timestamps, num_frames=nf_part, hist=hist, length_penalty=length_penalty)
+                        align=word_timestamps, num_frames=nf_part, hist=hist, length_penalty=length_penalty,
+                        token_logprobs=token_logprobs)
                     num_beams = nb_left  # (a sampling round left generation_config.num_beams = 1)
                     for j in range(R):  # (by position in the pass's batch, as transformers writes it)
                         do_cond[j] = bool(condition) and (temp_f[j] is None or temp_f[j] < 0.5)
@@ -1827,6 +1879,8 @@ class WhisperEngine:
                         if not known:
                             langs[i] = lang_f[j]
                         passes_raw[i].append(list(toks_f[j]))
+                        if token_logprobs:
+                            passes_lp[i].append(list(lp_f[j]))
                         snf = min(maxf[i] - seek[i], N_FRAMES)  # seek_num_frames
                         if skip_f[j]:  # generate(): seek += seek_num_frames, nothing kept
                             seek[i] += snf
@@ -1836,6 +1890,8 @@ class WhisperEngine:
                         seg_lists[i].extend(segment_slices(toks_f[j], st.timestamp_begin))
                         if word_timestamps:
                             self._add_times(tts[i], ts_f[j], prompt_len + L, len(seg_tokens), seek[i])
+                        if token_logprobs:  # (the kept tokens are a prefix of the pass's)
+                            tlps[i].extend(lp_f[j][: len(seg_tokens)])
                         seek[i] += offset
                     continue
                 if num_beams > 1:  # pre-encoded first pass: this part's windows sit at encoder rows b0..
@@ -1843,10 +1899,10 @@ class WhisperEngine:
                     res = self.beam_pass(R, num_beams, tail, given, mnew, use_timestamps=return_timestamps,
                                          enc_row0=b0 if pre else 0, r_enc=n_chunks if pre else R, prefix=pfx,
                                          align=word_timestamps, num_frames=nf_part, length_penalty=length_penalty,
-                                         **hist)
+                                         **hist, **lpkw)
                 else:
                     res = self.decode_pass(R, tail, given, mnew, use_timestamps=return_timestamps,
-                                           align=word_timestamps, num_frames=nf_part, prefix=pfx, **hist)
+                                           align=word_timestamps, num_frames=nf_part, prefix=pfx, **hist, **lpkw)
                 self._masked = False
                 for j in range(R):
                     do_cond[j] = bool(condition)
@@ -1861,6 +1917,9 @@ class WhisperEngine:
                     seg_lists[i].extend(segment_slices(seq, st.timestamp_begin))
                     if word_timestamps:
                         self._add_times(tts[i], res.token_ts[j], prompt_len + L, len(seg_tokens), seek[i])
+                    if token_logprobs:
+                        passes_lp[i].append(list(res.token_lp[j]))
+                        tlps[i].extend(res.token_lp[j][: len(seg_tokens)])
                     seek[i] += offset
             passes += 1
             if max_passes is not None and passes >= max_passes:
@@ -1870,6 +1929,8 @@ class WhisperEngine:
         self.last_langs = langs
         self.last_passes = passes_raw
         self.last_token_timestamps = tts if word_timestamps else None
+        self.last_pass_logprobs = passes_lp if token_logprobs else None
+        self.last_token_logprobs = tlps if token_logprobs else None
         return segs
 
     @staticmethod
@@ -1883,12 +1944,13 @@ class WhisperEngine:
                        windows: Sequence[int], pass_no: int, enc_row0: int = 0, r_enc: Optional[int] = None,
                        prefix=None, num_beams: int = 1, align: bool = False,
                        num_frames: Optional[Sequence[int]] = None, hist: Optional[dict] = None,
-                       length_penalty: float = 1.0):
+                       length_penalty: float = 1.0, token_logprobs: bool = False):
         """generate_with_fallback (generation_whisper.py:970-1116) for one seek pass of R encoded rows: decode at
         the first temperature, re-decode the rows whose criteria fail at the next one, until none does or the
         temperatures run out. Returns per row the kept sequence (EOS removed), should_skip, the language ids, each
         row's last temperature, the beam count left for the rest of the generate() call and (align) each row's token
-        times from the round that decided it (its round's batch: _postprocess_outputs per round, :1051).
+        times from the round that decided it (its round's batch: _postprocess_outputs per round, :1051) and
+        (token_logprobs) the kept sequence's per-token log-probabilities, from that same round.
         Bug-compatible with transformers: needs_fallback / should_skip are written at the row's position in the
         CURRENT (shrinking) subset, and the main loop reads should_skip by batch position (:1074-1088, :879); the
         no-speech probability of a retry round is read by subset position from the whole pass's (the processor's
@@ -1908,6 +1970,8 @@ class WhisperEngine:
         nb = num_beams
         ns_pass: Optional[List[float]] = None  # the first round's no-speech probabilities (the whole pass's rows)
         row_ts: List[Optional[np.ndarray]] = [None] * R
+        row_lp: List[Optional[List[float]]] = [None] * R
+        lpkw = {"token_logprobs": True} if token_logprobs else {}
         for fi, t in enumerate(temps):
             do_sample = t is not None and t > 0.0
             if do_sample:
@@ -1919,14 +1983,14 @@ class WhisperEngine:
                 res = self.beam_pass(len(idx), nb, tail, sub_lang, max_new, use_timestamps=return_timestamps,
                                      enc_rows=[enc_row0 + i for i in idx], r_enc=r_enc, prefix=sub_pfx,
                                      criteria=True, no_speech_token=ns_tok, align=align, num_frames=sub_nf,
-                                     length_penalty=length_penalty, **(hist or {}))
+                                     length_penalty=length_penalty, **(hist or {}), **lpkw)
             else:
                 res = self.sample_pass(len(idx), tail, sub_lang, max_new,
                                        temperature=float(t) if do_sample else 0.0, top_k=fb.top_k, seed=fb.seed,
                                        row_keys=[fallback_row_key(windows[i], pass_no, fi) for i in idx],
                                        use_timestamps=return_timestamps, enc_rows=[enc_row0 + i for i in idx],
                                        r_enc=r_enc, no_speech_token=ns_tok, prefix=sub_pfx, align=align,
-                                       num_frames=sub_nf, **(hist or {}))
+                                       num_frames=sub_nf, **(hist or {}), **lpkw)
             self._masked = False
             if align:
                 for j, i in enumerate(idx):
@@ -1945,12 +2009,15 @@ class WhisperEngine:
                 if seq and seq[-1] == st.eot:
                     seq = seq[:-1]
                 seqs[idx[j]] = seq
+                if token_logprobs:
+                    row_lp[idx[j]] = list(res.token_lp[j][: len(seq)])
                 if needs:
                     new_idx.append(idx[j])
             idx = new_idx
             if not idx or fi == len(temps) - 1:
                 break
-        return seqs, skip, langs if langs is not None else [None] * R, final_t, nb, (row_ts if align else None)
+        return (seqs, skip, langs if langs is not None else [None] * R, final_t, nb, (row_ts if align else None),
+                (row_lp if token_logprobs else None))
 
     @on_engine_streams
     def run_batches(self, sizes: Sequence[int], load=None, batch_kwargs: Optional[Sequence[dict]] = None,
@@ -1984,6 +2051,8 @@ class WhisperEngine:
         self.batch_passes = []
         self.batch_token_timestamps = []
         self.batch_prefixes = []
+        self.batch_pass_logprobs = []  # (generate(token_logprobs=True): last_pass_logprobs / last_token_logprobs)
+        self.batch_token_logprobs = []
         overlap = self.overlap  # False: encoder and decoder strictly in turn
         if sizes:
             prefetch(0)
@@ -2005,5 +2074,7 @@ class WhisperEngine:
             self.batch_passes.append(self.last_passes)
             self.batch_token_timestamps.append(self.last_token_timestamps)
             self.batch_prefixes.append(self.last_pass_prefixes)
+            self.batch_pass_logprobs.append(self.last_pass_logprobs)
+            self.batch_token_logprobs.append(self.last_token_logprobs)
         self.use_slot(0)
         return out

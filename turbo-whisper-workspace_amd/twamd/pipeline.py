@@ -125,8 +125,16 @@ class TurboTranscriber:
 
     def __call__(self, inputs: Union[str, bytes, np.ndarray, dict], *, chunk_length_s: float = 0,
                  stride_length_s=None, batch_size: int = 1, generate_kwargs: Optional[Dict[str, Any]] = None,
-                 return_timestamps: Union[bool, str] = False, return_language: bool = False, **kwargs) -> dict:
+                 return_timestamps: Union[bool, str] = False, return_language: bool = False,
+                 return_confidence: bool = False, **kwargs) -> dict:
+        """The HF ASR pipeline call. return_confidence (extension): the log-probability of every generated token
+        under its step's processed scores (WhisperEngine.generate(token_logprobs=True)) rides through the stitching
+        and comes out as each word's "probability" (return_timestamps="word": the mean of exp(lp) over the word's
+        tokens, openai-whisper's definition), each chunk's "avg_logprob" (return_timestamps=True) or the result's
+        "avg_logprob"; text, timestamps and chunks are those of the call without it. last_window_pass_logprobs then
+        sits beside last_window_passes."""
         word = return_timestamps == "word"
+        conf = bool(return_confidence)
         if return_timestamps == "char":
             raise ValueError("Whisper cannot return `char` timestamps, only word level or segment level timestamps.")
         gk = dict(generate_kwargs or {})
@@ -198,7 +206,7 @@ class TurboTranscriber:
             return self._long_form(wav, task=task, language=language, return_timestamps=return_timestamps,
                                    return_language=return_language, max_new_tokens=max_new_tokens,
                                    num_beams=num_beams, max_passes=max_passes, fallback=fallback, condition=cond,
-                                   prompt=prompt, history=hist)
+                                   prompt=prompt, history=hist, confidence=conf)
         else:
             windows = [Window(0, len(wav), 0, 0, True)]
             with_stride = False
@@ -216,28 +224,40 @@ class TurboTranscriber:
                       **({"condition_on_prev_tokens": True} if cond else {}),
                       **({"prompt": prompt} if prompt else {}),
                       **({"history": hist} if hist else {}),
-                      **({"group": batch_size} if grouped else {}))
+                      **({"group": batch_size} if grouped else {}),
+                      **({"token_logprobs": True} if conf else {}))
             if word:  # token times ride along as floats after the tokens (one all-gather carries both)
                 nf = [-(-min(x.length, CHUNK_SAMPLES) // 160) for x in ws]
                 toks = self.transcribe_windows(w, ws, word_timestamps=True, num_frames=nf, **kw)
-                return [(t, ts) for t, ts in zip(toks, self.last_window_token_timestamps)]
-            return self.transcribe_windows(w, ws, **kw)
+                lanes = [self.last_window_token_timestamps]
+            else:
+                toks = self.transcribe_windows(w, ws, **kw)
+                lanes = []
+            if conf:  # the log-probabilities ride the same way (0.0 beside the batch's right padding)
+                lanes.append([list(lp) + [0.0] * (len(t) - len(lp))
+                              for t, lp in zip(toks, self.last_window_token_logprobs)])
+            return [tuple(x) for x in zip(toks, *lanes)] if lanes else toks
 
         # one window shard per rank + one all-gather of the token arrays (twamd.dist); plain call on 1 GPU
-        outputs = dist.transcribe_sharded(run, wav, windows, timed=word) if sharded else run(wav, windows)
+        n_lanes = int(word) + int(conf)
+        outputs = dist.transcribe_sharded(run, wav, windows, timed=n_lanes) if sharded else run(wav, windows)
         model_outputs = []
         for w, toks in zip(windows, outputs):
-            if word:
-                toks, tts = toks
-                o = {"tokens": toks, "token_timestamps": tts}
-            else:
-                o = {"tokens": toks}
+            o = {}
+            if n_lanes:
+                toks, *fl = toks
+                if word:
+                    o["token_timestamps"] = fl[0]
+                if conf:
+                    o["token_logprobs"] = fl[-1]
+            o["tokens"] = toks
             if with_stride:
                 sr = self.sampling_rate
                 o["stride"] = (w.length / sr, w.stride_left / sr, w.stride_right / sr)
             model_outputs.append(o)
         kw = dict(return_timestamps="word" if word else bool(return_timestamps), return_language=return_language,
-                  time_precision=time_precision(self.engine.d.max_source_positions))
+                  time_precision=time_precision(self.engine.d.max_source_positions),
+                  **({"confidence": True} if conf else {}))
         # sharded: every rank stitches its own windows and the pieces are merged (dist.stitch_sharded: the serial
         # _decode_asr result, without rank 0 walking every window of the call)
         text, optional = (dist.stitch_sharded(self.vocab, model_outputs, **kw) if sharded else
@@ -256,7 +276,7 @@ class TurboTranscriber:
         return lt[tok]
 
     def _long_form(self, wav, *, task, language, return_timestamps, return_language, max_new_tokens, num_beams,
-                   max_passes, fallback, condition=False, prompt=None, history=None) -> dict:
+                   max_passes, fallback, condition=False, prompt=None, history=None, confidence=False) -> dict:
         """An input longer than 30 s without chunk_length_s: the pipeline hands generate() the features of the whole
         input (feature extractor with truncation=False, padding="longest", $TF/pipelines/automatic_speech_recognition
         .py:450-457) and generate() runs its seek loop over all of them (generation_whisper.py:647-968: is_shortform
@@ -275,6 +295,8 @@ class TurboTranscriber:
             kw.update(history or {})
             if word:  # num_frames: the feature extractor's attention mask, one per hop (_set_num_frames)
                 kw.update(word_timestamps=True, num_frames=[-(-int(x.shape[0]) // 160)])
+            if confidence:
+                kw.update(token_logprobs=True)
             toks = eng.generate(1, task=task, lang_ids=None if lang_id is None else [lang_id],
                                 max_new_tokens=max_new_tokens, return_timestamps=True, num_beams=num_beams,
                                 max_passes=max_passes, condition_on_prev_tokens=condition, **kw)[0]
@@ -287,9 +309,14 @@ class TurboTranscriber:
         if word:
             self.last_window_token_timestamps = list(eng.last_token_timestamps)
             out["token_timestamps"] = eng.last_token_timestamps[0]
+        if confidence:
+            self.last_window_pass_logprobs = list(eng.last_pass_logprobs)
+            self.last_window_token_logprobs = list(eng.last_token_logprobs)
+            out["token_logprobs"] = eng.last_token_logprobs[0]
         text, optional = decode_asr(self.vocab, [out], return_timestamps="word" if word else bool(return_timestamps),
                                     return_language=return_language,
-                                    time_precision=time_precision(self.engine.d.max_source_positions))
+                                    time_precision=time_precision(self.engine.d.max_source_positions),
+                                    **({"confidence": True} if confidence else {}))
         return {"text": text, **optional}
 
     def transcribe_windows(self, wav: np.ndarray, windows: Sequence[Window], task: Optional[str],
@@ -298,7 +325,8 @@ class TurboTranscriber:
                            num_frames: Optional[Sequence[int]] = None, group: Optional[int] = None,
                            max_passes: Optional[int] = None, fallback: Optional[FallbackConfig] = None,
                            window_base: int = 0, condition_on_prev_tokens: bool = False,
-                           prompt: Optional[dict] = None, history: Optional[dict] = None) -> List[List[int]]:
+                           prompt: Optional[dict] = None, history: Optional[dict] = None,
+                           token_logprobs: bool = False) -> List[List[int]]:
         """Log-mel + generate for every window; returns per-window token sequences (generate() output,
         right-padded with the pad token within each engine batch, as the HF batch output is). Batches of
         max_batch windows go through WhisperEngine.run_batches: batch k+1 is encoded while batch k decodes.
@@ -312,6 +340,10 @@ class TurboTranscriber:
 
         history: generate()'s repetition_penalty / no_repeat_ngram_size / length_penalty (those that are set), handed
         to every batch's generate(): per-pass token histories, so the results stay per-window.
+
+        token_logprobs: every batch's generate() also records the tokens' log-probabilities
+        (last_window_pass_logprobs beside last_window_passes, last_window_token_logprobs beside the returned tokens,
+        unpadded).
 
         wav: a host array, or a torch tensor (a rank's copy of the broadcast waveform, in device memory)."""
         eng = self.engine
@@ -352,7 +384,8 @@ class TurboTranscriber:
                               max_passes=max_passes,
                               **({"fallback": fallback, "window_offset": window_base} if fallback is not None else {}),
                               **({"condition_on_prev_tokens": True} if condition_on_prev_tokens else {}),
-                              **(prompt or {}), **(history or {}))
+                              **(prompt or {}), **(history or {}),
+                              **({"token_logprobs": True} if token_logprobs else {}))
         out: List[List[int]] = []
         for seqs in res:
             out.extend(pad_right(seqs, self.gen.special.eot))
@@ -362,6 +395,9 @@ class TurboTranscriber:
         self.last_window_prefixes = [p for bp in eng.batch_prefixes for p in bp]
         if word_timestamps:  # per window the concatenated segments' token times (not padded, as the pipeline's)
             self.last_window_token_timestamps = [t for bt in eng.batch_token_timestamps for t in bt]
+        if token_logprobs:
+            self.last_window_pass_logprobs = [p for bp in eng.batch_pass_logprobs for p in bp]
+            self.last_window_token_logprobs = [t for bt in eng.batch_token_logprobs for t in bt]
         return out
 
     @staticmethod

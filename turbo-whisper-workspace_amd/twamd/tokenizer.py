@@ -11,6 +11,7 @@
 from __future__ import annotations
 
 import json
+import math
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -145,15 +146,21 @@ class WhisperVocab:
         return "".join(out)
 
 
-def find_longest_common_sequence(sequences: List[List[int]], token_timestamp_sequences=None):
+def find_longest_common_sequence(sequences: List[List[int]], token_timestamp_sequences=None, aux_sequences=None):
     """Greedy overlap merge of consecutive token runs (the pipeline's stride stitching,
     $TF/models/whisper/tokenization_whisper.py:1153-1270). With token_timestamp_sequences (word timestamps) a match
     also needs the left token's (start, end) <= the right one's, the timestamps are split the same way, and the
-    result is (tokens, timestamps)."""
+    result is (tokens, timestamps). aux_sequences (one value per token of every sequence, e.g. log-probabilities):
+    an auxiliary sequence cut at the same indices as the tokens, which takes no part in the match (a wider
+    (start, end) tuple would change which tokens match); the result is then (tokens, timestamps or [], aux)."""
     left = sequences[0]
     left_len = len(left)
     total: List[int] = []
     with_ts = bool(token_timestamp_sequences)
+    with_aux = aux_sequences is not None
+    if with_aux:  # cut at the tokens' lmid / rmid below; never part of the match
+        left_aux = aux_sequences[0]
+        total_aux: list = []
     if with_ts:
         left_ts = token_timestamp_sequences[0]
         total_ts: list = []
@@ -197,7 +204,15 @@ def find_longest_common_sequence(sequences: List[List[int]], token_timestamp_seq
         if with_ts:
             total_ts.extend(left_ts[:lmid])
             left_ts = token_timestamp_sequences[seq_idx + 1][rmid:]
+        if with_aux:
+            total_aux.extend(left_aux[:lmid])
+            left_aux = aux_sequences[seq_idx + 1][rmid:]
     total.extend(left)
+    if with_aux:
+        total_aux.extend(left_aux)
+        if with_ts:
+            total_ts.extend(left_ts)
+        return total, (total_ts if with_ts else []), total_aux
     if token_timestamp_sequences is None:
         return total
     if with_ts:
@@ -274,8 +289,9 @@ def _merge_punctuations(words, tokens, indices, prepended="\"'“¡¿([{-", appe
 
 
 def collate_word_timestamps(vocab: "WhisperVocab", tokens: List[int], token_timestamps, language: Optional[str],
-                            return_language: bool) -> List[dict]:
-    """_collate_word_timestamps + _combine_tokens_into_words (:1273-1312)."""
+                            return_language: bool, token_logprobs: Optional[Sequence[float]] = None) -> List[dict]:
+    """_collate_word_timestamps + _combine_tokens_into_words (:1273-1312). token_logprobs (one per token): every
+    word dict also gets "probability" (word_probabilities)."""
     language = language or "english"
     if language in {"chinese", "japanese", "thai", "lao", "myanmar", "cantonese"}:
         words, wtoks, idx = _split_tokens_on_unicode(vocab, tokens)
@@ -283,8 +299,24 @@ def collate_word_timestamps(vocab: "WhisperVocab", tokens: List[int], token_time
         words, wtoks, idx = _split_tokens_on_spaces(vocab, tokens)
     _merge_punctuations(words, wtoks, idx)
     extra = {"language": language} if return_language else {}
-    return [{"text": w, "timestamp": (token_timestamps[ix[0]][0], token_timestamps[ix[-1]][1]), **extra}
-            for w, ix in zip(words, idx)]
+    out = [{"text": w, "timestamp": (token_timestamps[ix[0]][0], token_timestamps[ix[-1]][1]), **extra}
+           for w, ix in zip(words, idx)]
+    if token_logprobs is not None:
+        for d, p in zip(out, word_probabilities(idx, token_logprobs)):
+            d["probability"] = p
+    return out
+
+
+def word_probabilities(token_indices: Sequence[Sequence[int]], token_logprobs: Sequence[float]) -> List[float]:
+    """A word's probability as openai-whisper defines it: the arithmetic mean of exp(log-probability) over the
+    word's tokens (token_indices: per word the positions of its tokens, collate_word_timestamps' index lists)."""
+    return [float(np.mean([math.exp(float(token_logprobs[k])) for k in ix])) for ix in token_indices]
+
+
+def mean_logprob(token_logprobs: Sequence[float]) -> Optional[float]:
+    """avg_logprob of a run of resolved text tokens: their mean log-probability, None for an empty run."""
+    lps = [float(x) for x in token_logprobs]
+    return float(sum(lps) / len(lps)) if lps else None
 
 
 class AsrStitcher:
@@ -295,12 +327,19 @@ class AsrStitcher:
     with the other shards' (twamd.dist.stitch_sharded)."""
 
     def __init__(self, vocab: WhisperVocab, return_timestamps, return_language: bool = False,
-                 time_precision: float = 0.02, segment_size: int = 1500, state: Optional[dict] = None):
+                 time_precision: float = 0.02, segment_size: int = 1500, state: Optional[dict] = None,
+                 confidence: bool = False):
+        """confidence: every output carries "token_logprobs" (one float per entry of "tokens"); they ride beside
+        the text tokens through the stitching (never compared) and come out as each word's "probability", each
+        chunk's "avg_logprob" or the result's "avg_logprob" (assemble_asr). Text, timestamps and chunk boundaries
+        are those of the same outputs without it."""
         self.vocab, self.return_timestamps, self.return_language = vocab, return_timestamps, return_language
         self.time_precision, self.segment_size = time_precision, segment_size
         self.word = return_timestamps == "word"
+        self.conf = bool(confidence)
         self.chunks: List[dict] = []  # closed chunks, in order
-        st = state or self.initial_state()
+        st = state or self.initial_state(confidence=self.conf)
+        self.previous_token_aux = [list(t) for t in st.get("previous_token_aux", [])]
         self.chunk = {"language": st["chunk"]["language"], "timestamp": list(st["chunk"]["timestamp"]),
                       "text": st["chunk"]["text"]}
         self.previous_tokens = [list(t) for t in st["previous_tokens"]]
@@ -308,19 +347,39 @@ class AsrStitcher:
         self.skip, self.last_language, self.time_offset = st["skip"], st["last_language"], st["time_offset"]
 
     @staticmethod
-    def initial_state(last_language: Optional[str] = None, time_offset: float = 0.0) -> dict:
+    def initial_state(last_language: Optional[str] = None, time_offset: float = 0.0, confidence: bool = False) -> dict:
         """A clean state: no open chunk, nothing pending (what decode_asr starts from, and what holds after every
-        window whose last segment closed)."""
+        window whose last segment closed). confidence: the state of a stitcher that carries log-probabilities (one
+        more key, the pending runs' values)."""
         return {"chunk": {"language": last_language, "timestamp": [None, None], "text": ""}, "previous_tokens": [],
                 "previous_token_timestamps": [], "skip": False, "last_language": last_language,
-                "time_offset": time_offset}
+                "time_offset": time_offset, **({"previous_token_aux": []} if confidence else {})}
 
     def state(self) -> dict:
         return {"chunk": {"language": self.chunk["language"], "timestamp": list(self.chunk["timestamp"]),
                           "text": self.chunk["text"]},
                 "previous_tokens": [list(t) for t in self.previous_tokens],
                 "previous_token_timestamps": [[tuple(x) for x in t] for t in self.previous_token_timestamps],
-                "skip": self.skip, "last_language": self.last_language, "time_offset": self.time_offset}
+                "skip": self.skip, "last_language": self.last_language, "time_offset": self.time_offset,
+                **({"previous_token_aux": [list(t) for t in self.previous_token_aux]} if self.conf else {})}
+
+    def _resolve(self, chunk: dict, with_ts: bool) -> None:
+        """Close `chunk` over the pending token runs: its text, (word) its words, (confidence) its resolved tokens'
+        log-probabilities under "_lp" (assemble_asr turns them into the public keys)."""
+        vocab = self.vocab
+        if self.conf:
+            resolved, resolved_ts, lps = find_longest_common_sequence(
+                self.previous_tokens, self.previous_token_timestamps if with_ts else None, self.previous_token_aux)
+            chunk["_lp"] = lps
+        elif with_ts:
+            resolved, resolved_ts = find_longest_common_sequence(self.previous_tokens, self.previous_token_timestamps)
+            lps = None
+        else:
+            resolved, resolved_ts, lps = find_longest_common_sequence(self.previous_tokens), None, None
+        chunk["text"] = vocab.decode(resolved)
+        if with_ts and self.word:
+            chunk["words"] = collate_word_timestamps(vocab, resolved, resolved_ts, self.last_language,
+                                                     self.return_language, lps)
 
     def _new_chunk(self) -> dict:
         return {"language": self.last_language, "timestamp": [None, None], "text": ""}
@@ -335,6 +394,10 @@ class AsrStitcher:
         if token_ids and token_ids[0] == st.startofprev:
             token_ids = token_ids[token_ids.index(st.sot):] if st.sot in token_ids else []
         token_timestamps = list(output["token_timestamps"]) if word else None
+        token_lps = None
+        if self.conf:  # (cut with a stripped prompt: one value per remaining token)
+            token_lps = list(output["token_logprobs"])
+            token_lps = token_lps[len(token_lps) - len(token_ids):] if token_ids else []
         last_timestamp = None
         first_timestamp = timestamp_begin
         cur_max_timestamp = 0.0
@@ -354,6 +417,7 @@ class AsrStitcher:
                         last_timestamp = token
         current_tokens: List[int] = []
         current_token_timestamps: list = []
+        current_aux: list = []
         chunk = self.chunk
         for i, token in enumerate(token_ids):
             if token in special_ids:
@@ -362,11 +426,13 @@ class AsrStitcher:
                 if language is not None:
                     if self.last_language and language != self.last_language and not self.return_timestamps:
                         self.previous_tokens.append(current_tokens)
-                        resolved = find_longest_common_sequence(self.previous_tokens)
-                        chunk["text"] = vocab.decode(resolved)
+                        self.previous_token_aux.append(current_aux)
+                        self._resolve(chunk, False)
                         self.chunks.append(chunk)
                         self.previous_tokens = []
                         current_tokens = []
+                        self.previous_token_aux = []
+                        current_aux = []
                         chunk = self._new_chunk()
                     chunk["language"] = language
                     self.last_language = language
@@ -398,20 +464,20 @@ class AsrStitcher:
                         self.previous_tokens.append(current_tokens)
                         if word:
                             self.previous_token_timestamps.append(current_token_timestamps)
-                        resolved, resolved_ts = find_longest_common_sequence(self.previous_tokens,
-                                                                             self.previous_token_timestamps)
-                        chunk["text"] = vocab.decode(resolved)
-                        if word:
-                            chunk["words"] = collate_word_timestamps(vocab, resolved, resolved_ts, self.last_language,
-                                                                     self.return_language)
+                        self.previous_token_aux.append(current_aux)
+                        self._resolve(chunk, True)
                         self.chunks.append(chunk)
                         self.previous_tokens = []
                         current_tokens = []
                         self.previous_token_timestamps = []
                         current_token_timestamps = []
+                        self.previous_token_aux = []
+                        current_aux = []
                         chunk = self._new_chunk()
             else:
                 current_tokens.append(token)
+                if token_lps is not None:
+                    current_aux.append(float(token_lps[i]))
                 if word:
                     start = (round(0.0 + self.time_offset, 2) if i == 0
                              else round(token_timestamps[i - 1] + self.time_offset, 2))
@@ -422,29 +488,39 @@ class AsrStitcher:
             self.previous_tokens.append(current_tokens)
             if word:
                 self.previous_token_timestamps.append(current_token_timestamps)
+            self.previous_token_aux.append(current_aux)
         elif not any(p for p in self.previous_tokens):
             chunk = self._new_chunk()
             self.previous_tokens = []
             self.previous_token_timestamps = []
+            self.previous_token_aux = []
         self.chunk = chunk
 
     def finish(self) -> Tuple[str, dict]:
         chunks = list(self.chunks)
         if self.previous_tokens:
             chunk = self.chunk
-            resolved, resolved_ts = find_longest_common_sequence(self.previous_tokens, self.previous_token_timestamps)
-            chunk["text"] = self.vocab.decode(resolved)
-            if self.word:
-                chunk["words"] = collate_word_timestamps(self.vocab, resolved, resolved_ts, self.last_language,
-                                                         self.return_language)
+            self._resolve(chunk, True)
             chunks.append(chunk)
-        return assemble_asr(chunks, self.return_timestamps, self.return_language)
+        return assemble_asr(chunks, self.return_timestamps, self.return_language, self.conf)
 
 
-def assemble_asr(chunks: List[dict], return_timestamps, return_language: bool) -> Tuple[str, dict]:
-    """The tail of _decode_asr: the full text and the optional chunk / word list from the closed chunks."""
+def assemble_asr(chunks: List[dict], return_timestamps, return_language: bool,
+                 confidence: bool = False) -> Tuple[str, dict]:
+    """The tail of _decode_asr: the full text and the optional chunk / word list from the closed chunks.
+    confidence: the chunks' resolved log-probabilities ("_lp") become each chunk's "avg_logprob" with segment
+    timestamps, the result's "avg_logprob" over every resolved text token without timestamps (the words carry their
+    "probability" already)."""
     word = return_timestamps == "word"
     full_text = "".join(c["text"] for c in chunks)
+    top = {}
+    if confidence:
+        lps = [c.pop("_lp", []) for c in chunks]
+        if return_timestamps and not word:
+            for c, lp in zip(chunks, lps):
+                c["avg_logprob"] = mean_logprob(lp)
+        elif not return_timestamps:
+            top = {"avg_logprob": mean_logprob([x for lp in lps for x in lp])}
     if return_timestamps or return_language:
         for c in chunks:
             if not return_timestamps:
@@ -459,14 +535,16 @@ def assemble_asr(chunks: List[dict], return_timestamps, return_language: bool) -
             optional = {"chunks": chunks}
     else:
         optional = {}
-    return full_text, optional
+    return full_text, {**optional, **top}
 
 
 def decode_asr(vocab: WhisperVocab, outputs: Sequence[dict], return_timestamps, return_language: bool = False,
-               time_precision: float = 0.02, segment_size: int = 1500) -> Tuple[str, dict]:
+               time_precision: float = 0.02, segment_size: int = 1500, confidence: bool = False) -> Tuple[str, dict]:
     """outputs: [{"tokens": [ids...], "stride": (chunk_len_s, left_s, right_s) optional,
-    "token_timestamps": [s...] (return_timestamps="word")}, ...] in chunk order."""
-    stitcher = AsrStitcher(vocab, return_timestamps, return_language, time_precision, segment_size)
+    "token_timestamps": [s...] (return_timestamps="word"), "token_logprobs": [lp...] (confidence)}, ...] in chunk
+    order."""
+    stitcher = AsrStitcher(vocab, return_timestamps, return_language, time_precision, segment_size,
+                           confidence=confidence)
     for output in outputs:
         stitcher.feed(output)
     return stitcher.finish()
