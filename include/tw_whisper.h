@@ -486,6 +486,32 @@ int tw_logits_history(float* logits, int R, int ld_logits, int V, const int* pre
                       const int* prefix_len, const int* tokens, int ld_tokens, const int* state,
                       float repetition_penalty, int no_repeat_ngram, int to_logprobs, void* stream);
 
+/* tw_logits_history with generate()'s sequence_bias and bad_words_ids (SequenceBiasLogitsProcessor and
+ * NoBadWordsLogitsProcessor, $TF/generation/logits_process.py) in the same launch, on the same history. The stages
+ * run in generate()'s order: (to_logprobs) -> sequence bias, entries [0, n_pre) -> repetition penalty -> n-gram bans
+ * -> bad words, entries [n_pre, n_pre + n_post). An entry e is ids[e][0 .. len[e]) with bias[e]: a 1-id entry always
+ * adds its bias to its id; an entry of n ids adds it to its last id when the history holds at least n ids and ends
+ * in the entry's first n - 1 (an entry longer than the history is skipped, as transformers does). Entries of one
+ * stage that end in the same id add in table order, in f32, from 0.0 (put 1-id entries first: transformers adds
+ * those first), and the total is added to the score once; -inf is a legal bias and bad words are entries with bias
+ * -inf. A TW_HIST_LANG history slot compares as the detected language. An entry whose len is outside
+ * [1, ld_ids] or whose last id is outside [0, V) never fires. `table` is a HOST pointer (passed by value to the
+ * kernel; its arrays are device memory); NULL or n_pre + n_post == 0: exactly tw_logits_history. */
+#define TW_SEQBIAS_MAX_ENTRIES 256 /* n_pre + n_post */
+#define TW_SEQBIAS_MAX_IDS 16      /* ld_ids: ids per entry */
+typedef struct TwSeqBias {
+  const int32_t* ids; /* device int32[n_pre + n_post][ld_ids] */
+  const int32_t* len; /* device int32[n_pre + n_post] */
+  const float* bias;  /* device f32[n_pre + n_post] */
+  int32_t ld_ids;
+  int32_t n_pre;  /* sequence_bias entries, in front of the penalty */
+  int32_t n_post; /* bad_words_ids entries, behind the n-gram bans */
+} TwSeqBias;
+int tw_logits_history_bias(float* logits, int R, int ld_logits, int V, const int* prefix, int ld_prefix,
+                           const int* prefix_len, const int* tokens, int ld_tokens, const int* state,
+                           float repetition_penalty, int no_repeat_ngram, int to_logprobs, const TwSeqBias* table,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,13 +4,16 @@ detection, task token) + 128 generated tokens with EOS suppressed, i.e. 130 deco
 before, untimed. Prints one JSON line per (rows, mode).
 
     python scripts/decode_step_time.py [--rows 15 24 64] [--reps 3] [--fused 0 1] [--penalties 0 1] [--beams 12 5]
-                                       [--logprobs 0 1]
+                                       [--logprobs 0 1] [--seqbias 0 1]
 
 --fused 1: the decoder's layers as one persistent launch (tw_dec_fused) at every row count <= 32, 0: the launch chain
 (WhisperEngine.dec_fused_alone / dec_fused_max_rows overridden); with both, each row count runs both and reports
 whether their tokens agree.
 --penalties 1: the passes run with repetition_penalty=1.3 and no_repeat_ngram_size=3 (tw_logits_history queued ahead
 of every selection), 0: without; with both, the cost of the pre-pass is the difference of the two lines.
+--seqbias 1: the passes run with a 64-entry table of 1 to 4 ids each, 32 sequence_bias entries and 32 bad_words_ids
+(tw_logits_history_bias queued ahead of every selection; with --penalties 1 the same launch carries all four stages),
+0: without; the cost is the difference of the two lines.
 --logprobs 1: the passes run with token_logprobs (tw_token_logprob captured ahead of every selection; the beam pass
 with run_tlp / fin_tlp), 0: without; with both, the cost of the pre-kernel is the difference of the two lines.
 --beams W NB: also the beam pass of W windows x NB beams (one captured step per token: decoder step over W * NB rows,
@@ -24,6 +27,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "turbo-whisper-workspace_amd")]
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from twamd.config import PRESETS, GenerationSettings  # noqa: E402
@@ -44,6 +48,7 @@ def main():
     ap.add_argument("--penalties", type=int, nargs="+", default=[0])
     ap.add_argument("--beams", type=int, nargs=2, default=None, metavar=("W", "NB"))
     ap.add_argument("--logprobs", type=int, nargs="+", default=[0])
+    ap.add_argument("--seqbias", type=int, nargs="+", default=[0])
     a = ap.parse_args()
     dims = PRESETS["large-v3-turbo"]
     gen = GenerationSettings.default(dims)
@@ -54,14 +59,20 @@ def main():
     eng.wave[:B].copy_(torch.from_numpy(workload(B, 30.0, seed=1234)))
     eng.logmel(B)
     tail = eng.prompt_tail("transcribe", True)
+    # --seqbias: 64 entries of 1 to 4 text ids (seeded), the first 32 biased by +-2, the rest forbidden
+    rng = np.random.default_rng(7)
+    seqs = [[int(t) for t in rng.integers(1, gen.special.eot, 1 + e % 4)] for e in range(64)]
+    table = {"sequence_bias": [[ids, 2.0 if e % 2 else -2.0] for e, ids in enumerate(seqs[:32])],
+             "bad_words_ids": seqs[32:]}
     for R in a.rows:
         eng.row_map[:R] = torch.arange(R, dtype=torch.int32)
         eng.seek[:R] = 0
         eng.encode(R)
         torch.cuda.synchronize()
-        ref = {}  # per penalties value: the first mode's tokens
-        for fz, ce, gs, pen, lpo in [(f, c, g, p, q) for f in a.fused for c in a.check_every for g in a.graph_steps
-                                     for p in a.penalties for q in a.logprobs]:
+        ref = {}  # per (penalties, seqbias) value: the first mode's tokens
+        for fz, ce, gs, pen, lpo, sbo in [(f, c, g, p, q, b) for f in a.fused for c in a.check_every
+                                          for g in a.graph_steps for p in a.penalties for q in a.logprobs
+                                          for b in a.seqbias]:
             if fz and R > 32:
                 continue
             eng.dec_fused_alone = bool(fz)
@@ -71,6 +82,8 @@ def main():
             hk = {"repetition_penalty": 1.3, "no_repeat_ngram_size": 3} if pen else {}
             if lpo:
                 hk["token_logprobs"] = True
+            if sbo:
+                hk.update(table)
             eng.decode_pass(R, tail, None, 128, check_every=ce, **hk)  # warm-up: graph captures
             torch.cuda.synchronize()
             best = 1e9
@@ -83,10 +96,10 @@ def main():
             loop_us = min(e0.elapsed_time(e1) * 1e3 / n for e0, e1, n, _ in eng.pass_events)
             eng.pass_events = None
             print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs, "penalties": pen,
-                              "logprobs": lpo, "loop_us_per_step": round(loop_us, 1)}),
+                              "logprobs": lpo, "seqbias": sbo, "loop_us_per_step": round(loop_us, 1)}),
                   flush=True)
             assert all(len(t) == 128 for t in res.tokens)
-            ref.setdefault(pen, res.tokens)
+            ref.setdefault((pen, sbo), res.tokens)
             if a.slope:
                 eng.decode_pass(R, tail, None, 64, check_every=ce, **hk)
                 torch.cuda.synchronize()
@@ -101,8 +114,8 @@ def main():
                                   "slope_us_per_step": round((best - b64) * 1e6 / 64, 1),
                                   "fixed_ms": round((b64 - 66 * (best - b64) / 64) * 1e3, 2)}), flush=True)
             print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs, "penalties": pen,
-                              "logprobs": lpo, "pass_ms": round(best * 1e3, 2),
-                              "step_us": round(best * 1e6 / 130, 1), "tokens_equal": res.tokens == ref[pen]}),
+                              "logprobs": lpo, "seqbias": sbo, "pass_ms": round(best * 1e3, 2),
+                              "step_us": round(best * 1e6 / 130, 1), "tokens_equal": res.tokens == ref[(pen, sbo)]}),
                   flush=True)
     if a.beams:
         W, nb = a.beams

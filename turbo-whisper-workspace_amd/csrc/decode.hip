@@ -632,18 +632,53 @@ extern "C" int tw_token_prob(const float* logits, int B, int ld_logits, int V, i
 // The penalty touches each distinct id once, from the value before any penalty (only the first occurrence's thread
 // reads and writes its id); a barrier separates it from the bans, so -inf wins. IEEE f32 multiply / divide (no
 // fast-math in this build): the values equal torch's f32 bit for bit. Finished rows and columns [V, ld) are left alone.
+//
+// With a TwSeqBias table (BIAS; tw_logits_history_bias) two more stages run on the same staged history:
+// SequenceBiasLogitsProcessor in front of the penalty (entries [0, n_pre)) and NoBadWordsLogitsProcessor — the same
+// processor with -inf biases — behind the bans (entries [n_pre, n_pre + n_post)); generate()'s order is sequence bias,
+// penalty, n-gram, bad words. A thread per entry first decides whether the entry fires: a 1-id entry always does, an
+// entry of n ids when n <= L and its first n - 1 ids equal the history's last n - 1 (transformers skips
+// len > input_ids.shape[1], so n == L + 1 never fires although its prefix would fit). s_last[e] is the fired entry's
+// last id, else -1. Then, per stage, the first fired entry that ends in an id owns it: that thread alone adds the
+// fired entries' biases that end in the id in table order, from 0.0f, and does one row[id] += total. This is
+// transformers' f32 sum (bias = zeros; += length_1_bias — the host puts 1-id entries first —; += each matching entry in
+// dict order; scores + bias) without atomics and whatever the thread schedule; entries that do not fire add 0.0 there,
+// which changes no f32 sum that started from +0.0. Barriers separate the stages: they may touch the same id.
 // =================================================================================================
 #define TW_HIST_THREADS 1024
 #define TW_HIST_INFLIGHT 8  // logits of a thread's share loaded per trip (one load per trip serialised ~100 round trips)
+
+// one stage of the staged table, entries [e0, e1): see above
+__device__ inline void seqbias_stage(float* __restrict__ row, const int* s_last, const float* s_bias, int e0, int e1,
+                                     int tid) {
+  for (int e = e0 + tid; e < e1; e += TW_HIST_THREADS) {
+    const int id = s_last[e];
+    if (id < 0) continue;
+    // (both loops branch-free and unrolled, so that their LDS reads overlap: one read per trip serialised ~100 LDS
+    // round trips per stage; + 0.0f changes no total, which is never -0.0)
+    bool owner = true;
+#pragma unroll 8
+    for (int j = e0; j < e; ++j) owner &= (s_last[j] != id);
+    if (!owner) continue;
+    float total = 0.f;
+#pragma unroll 8
+    for (int j = e; j < e1; ++j) total += (s_last[j] == id) ? s_bias[j] : 0.f;
+    row[id] += total;
+  }
+}
+
+template <bool BIAS>
 __global__ __launch_bounds__(TW_HIST_THREADS) void k_logits_history(float* __restrict__ logits, int ld_logits, int V,
                                                                     const int* __restrict__ prefix, int ld_prefix,
                                                                     const int* __restrict__ prefix_len,
                                                                     const int* __restrict__ tokens, int ld_tokens,
                                                                     const int* __restrict__ state, float penalty,
-                                                                    int ngram, int to_logprobs) {
+                                                                    int ngram, int to_logprobs, TwSeqBias sb) {
   TW_DEC_PRIO();
   __shared__ int h[TW_HIST_MAX];
   __shared__ float red[2 * (TW_HIST_THREADS / 64)];
+  __shared__ int s_last[BIAS ? TW_SEQBIAS_MAX_ENTRIES : 1];
+  __shared__ float s_bias[BIAS ? TW_SEQBIAS_MAX_ENTRIES : 1];
   const int r = blockIdx.x, tid = threadIdx.x;
   const int* st = state + r * TW_STATE_STRIDE;
   if (st[TW_ST_FINISHED]) return;  // (uniform per block)
@@ -705,6 +740,31 @@ __global__ __launch_bounds__(TW_HIST_THREADS) void k_logits_history(float* __res
     }
   }
   __syncthreads();  // h is staged; the row's log-probabilities are written
+  if (BIAS) {
+    const int ne = sb.n_pre + sb.n_post;
+    for (int e = tid; e < ne; e += TW_HIST_THREADS) {
+      // the entry's row, length and bias are loaded together (a loop bounded by the loaded length would serialise
+      // one round trip per id)
+      const int* ids = sb.ids + (size_t)e * sb.ld_ids;
+      int idv[TW_SEQBIAS_MAX_IDS];
+#pragma unroll
+      for (int k = 0; k < TW_SEQBIAS_MAX_IDS; ++k) idv[k] = k < sb.ld_ids ? ids[k] : -1;
+      const int n = sb.len[e];
+      const float b = sb.bias[e];
+      bool fires = n >= 1 && n <= sb.ld_ids && (n == 1 || n <= L);
+      int last = -1;
+#pragma unroll
+      for (int k = 0; k < TW_SEQBIAS_MAX_IDS; ++k) {
+        if (k < n - 1) fires = fires && (h[L - (n - 1) + k] == idv[k]);  // (fires: n <= L, the index is in [0, L))
+        if (k == n - 1) last = idv[k];
+      }
+      s_last[e] = (fires && last >= 0 && last < V) ? last : -1;
+      s_bias[e] = b;
+    }
+    __syncthreads();
+    seqbias_stage(row, s_last, s_bias, 0, sb.n_pre, tid);
+    __syncthreads();  // the penalty reads the biased values
+  }
   if (penalty != 1.0f) {
     for (int i = tid; i < L; i += TW_HIST_THREADS) {
       const int id = h[i];
@@ -726,21 +786,52 @@ __global__ __launch_bounds__(TW_HIST_THREADS) void k_logits_history(float* __res
       if (match && id >= 0 && id < V) row[id] = -INFINITY;
     }
   }
+  if (BIAS) {
+    __syncthreads();  // bad words come after the bans
+    seqbias_stage(row, s_last, s_bias, sb.n_pre, sb.n_pre + sb.n_post, tid);
+  }
 }
 
-extern "C" int tw_logits_history(float* logits, int R, int ld_logits, int V, const int* prefix, int ld_prefix,
-                                 const int* prefix_len, const int* tokens, int ld_tokens, const int* state,
-                                 float repetition_penalty, int no_repeat_ngram, int to_logprobs, void* stream) {
+extern "C" int tw_logits_history_bias(float* logits, int R, int ld_logits, int V, const int* prefix, int ld_prefix,
+                                      const int* prefix_len, const int* tokens, int ld_tokens, const int* state,
+                                      float repetition_penalty, int no_repeat_ngram, int to_logprobs,
+                                      const TwSeqBias* table, void* stream) {
   TW_REQUIRE(logits && tokens && state && R > 0, "tw_logits_history: bad args");
   TW_REQUIRE(V > 0 && V <= ld_logits, "tw_logits_history: V=%d ld=%d", V, ld_logits);
   TW_REQUIRE((prefix == nullptr) == (prefix_len == nullptr) && ld_prefix >= 0 && ld_tokens >= 0,
              "tw_logits_history: prefix / prefix_len go together (ld_prefix=%d ld_tokens=%d)", ld_prefix, ld_tokens);
   TW_REQUIRE(repetition_penalty > 0.f && repetition_penalty == repetition_penalty && no_repeat_ngram >= 0,
              "tw_logits_history: repetition_penalty=%f no_repeat_ngram=%d", repetition_penalty, no_repeat_ngram);
-  hipLaunchKernelGGL(k_logits_history, dim3(R), dim3(TW_HIST_THREADS), 0, (hipStream_t)stream, logits, ld_logits, V,
-                     prefix, ld_prefix, prefix_len, tokens, ld_tokens, state, repetition_penalty, no_repeat_ngram,
-                     to_logprobs);
+  TwSeqBias sb = {};
+  if (table) {
+    TW_REQUIRE(table->n_pre >= 0 && table->n_post >= 0 && table->n_pre <= TW_SEQBIAS_MAX_ENTRIES &&
+                   table->n_post <= TW_SEQBIAS_MAX_ENTRIES && table->n_pre + table->n_post <= TW_SEQBIAS_MAX_ENTRIES,
+               "tw_logits_history_bias: n_pre=%d + n_post=%d entries exceed TW_SEQBIAS_MAX_ENTRIES=%d", table->n_pre,
+               table->n_post, TW_SEQBIAS_MAX_ENTRIES);
+    if (table->n_pre + table->n_post > 0) {
+      TW_REQUIRE(table->ld_ids >= 1 && table->ld_ids <= TW_SEQBIAS_MAX_IDS,
+                 "tw_logits_history_bias: ld_ids=%d (1 .. TW_SEQBIAS_MAX_IDS=%d ids per entry)", table->ld_ids,
+                 TW_SEQBIAS_MAX_IDS);
+      TW_REQUIRE(table->ids && table->len && table->bias, "tw_logits_history_bias: table arrays missing");
+      sb = *table;
+    }
+  }
+  if (sb.n_pre + sb.n_post > 0)
+    hipLaunchKernelGGL(k_logits_history<true>, dim3(R), dim3(TW_HIST_THREADS), 0, (hipStream_t)stream, logits,
+                       ld_logits, V, prefix, ld_prefix, prefix_len, tokens, ld_tokens, state, repetition_penalty,
+                       no_repeat_ngram, to_logprobs, sb);
+  else
+    hipLaunchKernelGGL(k_logits_history<false>, dim3(R), dim3(TW_HIST_THREADS), 0, (hipStream_t)stream, logits,
+                       ld_logits, V, prefix, ld_prefix, prefix_len, tokens, ld_tokens, state, repetition_penalty,
+                       no_repeat_ngram, to_logprobs, sb);
   return tw_check_launch("tw_logits_history");
+}
+
+extern "C" int tw_logits_history(float* logits, int R, int ld_logits, int V, const int* prefix, int ld_prefix,
+                                 const int* prefix_len, const int* tokens, int ld_tokens, const int* state,
+                                 float repetition_penalty, int no_repeat_ngram, int to_logprobs, void* stream) {
+  return tw_logits_history_bias(logits, R, ld_logits, V, prefix, ld_prefix, prefix_len, tokens, ld_tokens, state,
+                                repetition_penalty, no_repeat_ngram, to_logprobs, nullptr, stream);
 }
 
 // =================================================================================================

@@ -316,9 +316,11 @@ void logits_select_(const Tensor& logits, const Tensor& suppress_bits, at::IntAr
 
 // RepetitionPenaltyLogitsProcessor + NoRepeatNGramLogitsProcessor on the rows' history (prefix ++ generated tokens),
 // in place ahead of the selection ops (tw_logits_history); to_logprobs: log_softmax first (beam rows)
-void logits_history_(Tensor& logits, int64_t V, const c10::optional<Tensor>& prefix,
-                     const c10::optional<Tensor>& prefix_len, const Tensor& tokens, const Tensor& state,
-                     double repetition_penalty, int64_t no_repeat_ngram, bool to_logprobs) {
+// (table: the TwSeqBias of logits_history_bias_, or nullptr)
+void logits_history_impl(Tensor& logits, int64_t V, const c10::optional<Tensor>& prefix,
+                         const c10::optional<Tensor>& prefix_len, const Tensor& tokens, const Tensor& state,
+                         double repetition_penalty, int64_t no_repeat_ngram, bool to_logprobs,
+                         const TwSeqBias* table) {
   TW_OP_DEVICE(logits);
   dev(logits, at::kFloat, "logits");
   rows(logits, "logits");
@@ -339,12 +341,50 @@ void logits_history_(Tensor& logits, int64_t V, const c10::optional<Tensor>& pre
     TORCH_CHECK(prefix->size(0) >= R, "prefix must hold R rows");
     holds(logits, *prefix_len, at::kInt, R, "prefix_len");
   }
-  ok(tw_logits_history(ptr<float>(logits), (int)R, (int)logits.stride(0), (int)V,
-                       has_prefix ? ptr<int>(*prefix) : nullptr, has_prefix ? (int)prefix->stride(0) : 0,
-                       has_prefix ? ptr<int>(*prefix_len) : nullptr, ptr<int>(tokens), (int)tokens.stride(0),
-                       ptr<int>(state), (float)repetition_penalty, (int)no_repeat_ngram, to_logprobs ? 1 : 0,
-                       cur_stream(logits)),
+  ok(tw_logits_history_bias(ptr<float>(logits), (int)R, (int)logits.stride(0), (int)V,
+                            has_prefix ? ptr<int>(*prefix) : nullptr, has_prefix ? (int)prefix->stride(0) : 0,
+                            has_prefix ? ptr<int>(*prefix_len) : nullptr, ptr<int>(tokens), (int)tokens.stride(0),
+                            ptr<int>(state), (float)repetition_penalty, (int)no_repeat_ngram, to_logprobs ? 1 : 0,
+                            table, cur_stream(logits)),
      "logits_history");
+}
+
+void logits_history_(Tensor& logits, int64_t V, const c10::optional<Tensor>& prefix,
+                     const c10::optional<Tensor>& prefix_len, const Tensor& tokens, const Tensor& state,
+                     double repetition_penalty, int64_t no_repeat_ngram, bool to_logprobs) {
+  logits_history_impl(logits, V, prefix, prefix_len, tokens, state, repetition_penalty, no_repeat_ngram, to_logprobs,
+                      nullptr);
+}
+
+// logits_history_ with generate()'s sequence_bias (the table's first n_pre entries, ahead of the penalty) and
+// bad_words_ids (its next n_post entries, behind the n-gram bans): bias_ids int32[n][<= 16] (addressed by its row
+// stride), bias_len int32[n], bias f32[n], n >= n_pre + n_post (tw_logits_history_bias)
+void logits_history_bias_(Tensor& logits, int64_t V, const c10::optional<Tensor>& prefix,
+                          const c10::optional<Tensor>& prefix_len, const Tensor& tokens, const Tensor& state,
+                          double repetition_penalty, int64_t no_repeat_ngram, bool to_logprobs, const Tensor& bias_ids,
+                          const Tensor& bias_len, const Tensor& bias, int64_t n_pre, int64_t n_post) {
+  TORCH_CHECK(n_pre >= 0 && n_post >= 0 && n_pre + n_post <= TW_SEQBIAS_MAX_ENTRIES, "n_pre + n_post: 0 .. ",
+              TW_SEQBIAS_MAX_ENTRIES, " entries");
+  const int64_t n = n_pre + n_post;
+  dev(bias_ids, at::kInt, "bias_ids");
+  same_device(logits, bias_ids, "bias_ids");
+  rows(bias_ids, "bias_ids");
+  TORCH_CHECK(bias_ids.size(0) >= n && bias_ids.size(1) >= 1 && bias_ids.stride(0) >= bias_ids.size(1) &&
+                  bias_ids.stride(0) <= TW_SEQBIAS_MAX_IDS,
+              "bias_ids: [>= n_pre + n_post][>= 1] with a row stride of at most ", TW_SEQBIAS_MAX_IDS);
+  holds(logits, bias_len, at::kInt, n, "bias_len");
+  holds(logits, bias, at::kFloat, n, "bias");
+  TwSeqBias t;
+  t.ids = ptr<int>(bias_ids);
+  t.len = ptr<int>(bias_len);
+  t.bias = ptr<float>(bias);
+  // (a column view of a wider table is addressed by its row stride; the kernel reads ids[e][0 .. len[e]) with
+  // len[e] <= that stride, inside the table the view was cut from)
+  t.ld_ids = (int32_t)bias_ids.stride(0);
+  t.n_pre = (int32_t)n_pre;
+  t.n_post = (int32_t)n_post;
+  logits_history_impl(logits, V, prefix, prefix_len, tokens, state, repetition_penalty, no_repeat_ngram, to_logprobs,
+                      &t);
 }
 
 }  // namespace
@@ -372,6 +412,9 @@ TORCH_LIBRARY(tw, m) {
         "Tensor(c!) ids, Tensor(d!) pos, Tensor(e!) workspace) -> ()");
   m.def("logits_history_(Tensor(a!) logits, int V, Tensor? prefix, Tensor? prefix_len, Tensor tokens, Tensor state, "
         "float repetition_penalty, int no_repeat_ngram, bool to_logprobs) -> ()");
+  m.def("logits_history_bias_(Tensor(a!) logits, int V, Tensor? prefix, Tensor? prefix_len, Tensor tokens, "
+        "Tensor state, float repetition_penalty, int no_repeat_ngram, bool to_logprobs, Tensor bias_ids, "
+        "Tensor bias_len, Tensor bias, int n_pre, int n_post) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(tw, CUDA, m) {  // (the dispatch key of device tensors; on this ROCm build they are HIP tensors)
@@ -389,6 +432,7 @@ TORCH_LIBRARY_IMPL(tw, CUDA, m) {  // (the dispatch key of device tensors; on th
   m.impl("attn_decode_cross_out", &attn_decode_cross_out);
   m.impl("logits_select_", &logits_select_);
   m.impl("logits_history_", &logits_history_);
+  m.impl("logits_history_bias_", &logits_history_bias_);
 }
 
 TORCH_LIBRARY_IMPL(tw, Meta, m) {  // shape functions (FakeTensor / tracing); the out= and in-place ops write nothing
@@ -412,4 +456,7 @@ TORCH_LIBRARY_IMPL(tw, Meta, m) {  // shape functions (FakeTensor / tracing); th
                               Tensor&, Tensor&, Tensor&) {});
   m.impl("logits_history_", [](Tensor&, int64_t, const c10::optional<Tensor>&, const c10::optional<Tensor>&,
                                const Tensor&, const Tensor&, double, int64_t, bool) {});
+  m.impl("logits_history_bias_", [](Tensor&, int64_t, const c10::optional<Tensor>&, const c10::optional<Tensor>&,
+                                    const Tensor&, const Tensor&, double, int64_t, bool, const Tensor&, const Tensor&,
+                                    const Tensor&, int64_t, int64_t) {});
 }

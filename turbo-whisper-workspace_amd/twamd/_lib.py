@@ -34,6 +34,8 @@ TW_ST_NGEN, TW_ST_LAST, TW_ST_PENULT, TW_ST_LASTTS, TW_ST_FINISHED, TW_ST_LANG =
 TW_ST_SUMLP, TW_ST_NOSPEECH = 6, 7  # f32 bits (tw_logits_sample / tw_token_prob)
 TW_HIST_MAX = 448   # tw_logits_history: ids per row history (prefix + generated)
 TW_HIST_LANG = -1   # a prefix entry that reads the detected language, state[r][TW_ST_LANG]
+TW_SEQBIAS_MAX_ENTRIES = 256  # tw_logits_history_bias: sequence_bias + bad_words_ids entries
+TW_SEQBIAS_MAX_IDS = 16       # ids per entry
 
 # every symbol include/tw_whisper.h + include/tw_audio.h declare (tests check the .so exports all of them)
 EXPORTED = (
@@ -55,6 +57,7 @@ EXPORTED = (
     "tw_aac_adts_probe", "tw_aac_adts_decode", "tw_dec_fused", "tw_dec_fused_sync_bytes", "tw_dec_fused_supported",
     "tw_dec_fused_set_grid", "tw_dec_fused_set_acquire", "tw_dec_fused_set_probe", "tw_dec_fused_grid",
     "tw_dec_fused_xpart_bytes", "tw_logits_history", "tw_token_logprob", "tw_logits_sample_lp",
+    "tw_logits_history_bias",
 )
 
 
@@ -78,6 +81,11 @@ class TwBeamState(ctypes.Structure):
                 ("src_rows", ctypes.c_void_p), ("kv_tab", ctypes.c_void_p), ("fin_tab", ctypes.c_void_p),
                 ("run_lp", ctypes.c_void_p), ("fin_lp", ctypes.c_void_p),
                 ("run_tlp", ctypes.c_void_p), ("fin_tlp", ctypes.c_void_p)]
+
+
+class TwSeqBias(ctypes.Structure):
+    _fields_ = [("ids", ctypes.c_void_p), ("len", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("ld_ids", ctypes.c_int32), ("n_pre", ctypes.c_int32), ("n_post", ctypes.c_int32)]
 
 
 class TwFlacInfo(ctypes.Structure):
@@ -170,6 +178,8 @@ _SIGS = {
     "tw_token_logprob": ([_P, _I, _I, _P, ctypes.POINTER(TwSelectParams), _P, _P, _I, _P], _I),
     "tw_token_prob": ([_P, _I, _I, _I, _I, _P, _P], _I),
     "tw_logits_history": ([_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _F, _I, _I, _P], _I),
+    "tw_logits_history_bias": ([_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _F, _I, _I, ctypes.POINTER(TwSeqBias), _P],
+                               _I),
     "tw_gemm_bf16_partial": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P], _I),
     "tw_gemv_set_wide_slices": ([_I], _I),
     "tw_gemv_set_variant": ([_I], _I),

@@ -31,4 +31,4 @@ def load():
 
 OPS = ("logmel", "logmel_out", "gemm_bf16", "gemm_bf16_out", "attn_encoder", "attn_encoder_out", "layernorm",
        "layernorm_out", "gemv_packed_out", "resid_layernorm_packed_", "attn_decode_self_", "attn_decode_cross_out",
-       "logits_select_", "logits_history_")
+       "logits_select_", "logits_history_", "logits_history_bias_")

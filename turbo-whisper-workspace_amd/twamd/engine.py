@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, _ops, alignment
+from . import _lib, _ops, alignment, seqbias
 from .config import GenerationSettings, WhisperDims
 from .frontend import CHUNK_SAMPLES, N_FRAMES, dft_basis, mel_table, pack_k8
 from .segments import (FallbackConfig, condition_prefixes, fallback_sequence, need_fallback, retrieve_segment,
@@ -316,6 +316,13 @@ class WhisperEngine:
         self._hist_prefix = torch.zeros(self.max_rows, T, dtype=i32, device=dev)
         self._hist_len = torch.zeros(self.max_rows, dtype=i32, device=dev)
         self._hist: Optional[tuple] = None
+        # sequence_bias / bad_words_ids (tw_logits_history_bias): the entry table, sized to the kernel's limits so that
+        # the addresses captured graphs hold never change; a pass rewrites the contents (_bias_key: what they hold now)
+        # and the counts, captured by value, ride in _hist and with it in every graph key
+        self._bias_ids = torch.zeros(_lib.TW_SEQBIAS_MAX_ENTRIES, _lib.TW_SEQBIAS_MAX_IDS, dtype=i32, device=dev)
+        self._bias_len = torch.zeros(_lib.TW_SEQBIAS_MAX_ENTRIES, dtype=i32, device=dev)
+        self._bias_val = torch.zeros(_lib.TW_SEQBIAS_MAX_ENTRIES, dtype=torch.float32, device=dev)
+        self._bias_key: Optional[tuple] = None
         # the library's (tw_gemv_set_wide_slices, tw_gemv_set_variant) state (its defaults) and whether the decoder's
         # layers run as one persistent launch (tw_dec_fused) in the current pass
         self._dec_ctx = (1, 0, False)
@@ -937,15 +944,41 @@ class WhisperEngine:
                   ctypes.byref(params), v.state.data_ptr(), v.tokens.data_ptr() if tokens else None,
                   v.tokens.shape[1], v.ids.data_ptr(), v.pos.data_ptr(), v.sel_ws.data_ptr(), v.stream.cuda_stream)
 
+    def _bias_begin(self, sequence_bias, bad_words_ids) -> tuple:
+        """Checks the pass's sequence_bias / bad_words_ids (transformers' checks and messages, twamd.seqbias), writes
+        them to the table buffers in the kernel's order when those hold something else, and returns
+        (n_pre, n_post)."""
+        if sequence_bias is None and bad_words_ids is None:
+            return 0, 0
+        V = self.d.vocab
+        pre = seqbias.sequence_bias_entries(sequence_bias, V) if sequence_bias is not None else []
+        post = seqbias.bad_words_entries(bad_words_ids, self.gen.special.eot, V) if bad_words_ids is not None else []
+        seqbias.check_limits(pre, post)
+        entries = pre + post
+        key = tuple(entries)
+        if entries and key != self._bias_key:
+            n = len(entries)
+            ids = np.zeros((n, _lib.TW_SEQBIAS_MAX_IDS), np.int32)
+            for e, (seq, _) in enumerate(entries):
+                ids[e, : len(seq)] = seq
+            # (queued on the decoder stream behind the passes that read the previous contents)
+            self._bias_ids[:n] = torch.from_numpy(ids).to(self.device)
+            self._bias_len[:n] = torch.tensor([len(seq) for seq, _ in entries], dtype=torch.int32, device=self.device)
+            self._bias_val[:n] = torch.tensor([b for _, b in entries], dtype=torch.float32, device=self.device)
+            self._bias_key = key
+        return len(pre), len(post)
+
     def _hist_begin(self, R: int, repetition_penalty: float, no_repeat_ngram_size: int, tail: Sequence[int],
-                    lang_ids: Optional[Sequence[int]], prefix=None) -> None:
+                    lang_ids: Optional[Sequence[int]], prefix=None, sequence_bias=None, bad_words_ids=None) -> None:
         """Start a pass's token history for tw_logits_history: rows [0, R) of the prefix buffer take what
         transformers hands its processors as decoder_input_ids before the first generated token — the pass's prefix
         rows (prompt_ids / conditioned previous segments, left pads included), <|startoftranscript|>, the language
-        (TW_HIST_LANG when the pass detects it: the kernel reads state[r][TW_ST_LANG]) and the tail. With both
-        options off nothing is copied and no pre-pass is launched (_hist None)."""
+        (TW_HIST_LANG when the pass detects it: the kernel reads state[r][TW_ST_LANG]) and the tail. With every
+        option off nothing is copied and no pre-pass is launched (_hist None). sequence_bias / bad_words_ids: the
+        pass's entry table (_bias_begin); _hist then also carries its two counts."""
         p, n = float(repetition_penalty or 1.0), int(no_repeat_ngram_size or 0)
-        if p == 1.0 and n == 0:
+        n_pre, n_post = self._bias_begin(sequence_bias, bad_words_ids)
+        if p == 1.0 and n == 0 and n_pre + n_post == 0:
             self._hist = None
             return
         st = self.gen.special
@@ -962,18 +995,24 @@ class WhisperEngine:
             raise ValueError(f"decoder prompt of {L} tokens exceeds {self._hist_prefix.shape[1]} positions")
         self._hist_prefix[:R, :L] = torch.as_tensor(rows, dtype=torch.int32, device=self.device)
         self._hist_len[:R] = L
-        self._hist = (p, n)
+        self._hist = (p, n, n_pre, n_post) if n_pre + n_post else (p, n)
 
     def _history(self, r0: int, R: int, stream, to_logprobs: bool = False) -> None:
         """The history processors (repetition penalty, no-repeat n-gram) on the logits of rows [r0, r0 + R), in
-        place, when the pass set them (tw_logits_history; to_logprobs: beam rows, log_softmax first)."""
+        place, when the pass set them (tw_logits_history; to_logprobs: beam rows, log_softmax first). With a
+        sequence_bias / bad_words_ids table the same launch also runs those two stages (tw_logits_history_bias)."""
         if self._hist is None:
             return
-        p, n = self._hist
-        _lib.call("tw_logits_history", self.logits[r0:].data_ptr(), R, self.logits.stride(0), self.d.vocab,
-                  self._hist_prefix[r0:].data_ptr(), self._hist_prefix.stride(0), self._hist_len[r0:].data_ptr(),
-                  self.tokens[r0:].data_ptr(), self.tokens.stride(0), self.state[r0:].data_ptr(), p, n,
-                  int(to_logprobs), stream.cuda_stream)
+        p, n = self._hist[:2]
+        args = (self.logits[r0:].data_ptr(), R, self.logits.stride(0), self.d.vocab,
+                self._hist_prefix[r0:].data_ptr(), self._hist_prefix.stride(0), self._hist_len[r0:].data_ptr(),
+                self.tokens[r0:].data_ptr(), self.tokens.stride(0), self.state[r0:].data_ptr(), p, n, int(to_logprobs))
+        if len(self._hist) == 2:
+            _lib.call("tw_logits_history", *args, stream.cuda_stream)
+            return
+        table = _lib.TwSeqBias(self._bias_ids.data_ptr(), self._bias_len.data_ptr(), self._bias_val.data_ptr(),
+                               self._bias_ids.stride(0), self._hist[2], self._hist[3])
+        _lib.call("tw_logits_history_bias", *args, ctypes.byref(table), stream.cuda_stream)
 
     # Teacher-forcing hook of decode_pass (parity harness, tests/test_gpu_turbo.py and bench.py's parity leg):
     # hook(k, view) runs on the host after the step that produced generated position k (view None: the prompt's last
@@ -1163,7 +1202,8 @@ class WhisperEngine:
     def decode_pass(self, R: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]], max_new: int,
                     check_every: int = 8, use_timestamps: bool = True, align: bool = False,
                     num_frames: Optional[Sequence[int]] = None, prefix=None, repetition_penalty: float = 1.0,
-                    no_repeat_ngram_size: int = 0, token_logprobs: bool = False) -> PassResult:
+                    no_repeat_ngram_size: int = 0, token_logprobs: bool = False, sequence_bias=None,
+                    bad_words_ids=None) -> PassResult:
         """Greedy decode of R rows from the prompt [SOT, (lang), *tail] (the init tokens of
         _retrieve_init_tokens; the language is detected from the SOT step when lang_ids is None on a
         multilingual model). Returns the generated tokens of every row; with align, also every row's token-level
@@ -1178,7 +1218,8 @@ class WhisperEngine:
             try:
                 res = self.decode_pass(R, tail, lang_ids, max_new, check_every, use_timestamps, prefix=prefix,
                                        repetition_penalty=repetition_penalty,
-                                       no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs)
+                                       no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs,
+                                       sequence_bias=sequence_bias, bad_words_ids=bad_words_ids)
                 self._token_ts(R, P, res, num_frames)
                 return res
             finally:
@@ -1188,7 +1229,8 @@ class WhisperEngine:
             try:
                 res = self.decode_pass(R, tail, lang_ids, max_new, check_every, use_timestamps, prefix=prefix,
                                        repetition_penalty=repetition_penalty,
-                                       no_repeat_ngram_size=no_repeat_ngram_size)
+                                       no_repeat_ngram_size=no_repeat_ngram_size,
+                                       sequence_bias=sequence_bias, bad_words_ids=bad_words_ids)
             finally:
                 self._tlp = False
             lp = self.token_lp[:R].tolist()
@@ -1201,7 +1243,8 @@ class WhisperEngine:
         detect = st.is_multilingual and lang_ids is None
         params = self._select_params(0, max_new, use_timestamps)
         base = self._prefill(R, prefix)  # (condition_on_prev_tokens: the init tokens start at position base)
-        self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail, lang_ids, prefix)
+        self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail, lang_ids, prefix, sequence_bias,
+                         bad_words_ids)
 
         def prompt() -> None:
             """State reset, the prompt steps [SOT, (lang), *tail] and the first generated token (one token per
@@ -1338,7 +1381,8 @@ class WhisperEngine:
                     use_timestamps: bool = True, enc_rows: Optional[Sequence[int]] = None, r_enc: Optional[int] = None,
                     no_speech_token: Optional[int] = None, check_every: int = 8, prefix=None, align: bool = False,
                     num_frames: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
-                    no_repeat_ngram_size: int = 0, token_logprobs: bool = False) -> PassResult:
+                    no_repeat_ngram_size: int = 0, token_logprobs: bool = False, sequence_bias=None,
+                    bad_words_ids=None) -> PassResult:
         """One decode pass of the temperature-fallback loop (WhisperGenerationMixin.generate_with_fallback,
         generation_whisper.py:970-1116), eager, one tw_logits_sample per token: greedy when temperature == 0
         (the tokens of decode_pass), else a draw from softmax(processed / T) over the top_k scores. Per row it also
@@ -1355,7 +1399,8 @@ class WhisperEngine:
                 res = self.sample_pass(R, tail, lang_ids, max_new, temperature, top_k, seed, row_keys, use_timestamps,
                                        enc_rows, r_enc, no_speech_token, check_every, prefix,
                                        repetition_penalty=repetition_penalty,
-                                       no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs)
+                                       no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs,
+                                       sequence_bias=sequence_bias, bad_words_ids=bad_words_ids)
                 self._token_ts(R, P, res, num_frames)
                 return res
             finally:
@@ -1377,7 +1422,8 @@ class WhisperEngine:
             self._row_group = 1
         try:
             base = self._prefill(R, prefix, r_enc)
-            self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail, lang_ids, prefix)
+            self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail, lang_ids, prefix, sequence_bias,
+                             bad_words_ids)
             self.state[:R].zero_()
             self.state[:R, _lib.TW_ST_LAST:_lib.TW_ST_LASTTS + 1] = -1
             self.pos[:R] = base
@@ -1470,7 +1516,8 @@ class WhisperEngine:
                   enc_row0: int = 0, r_enc: Optional[int] = None, prefix=None, align: bool = False,
                   num_frames: Optional[Sequence[int]] = None, enc_rows: Optional[Sequence[int]] = None,
                   criteria: bool = False, no_speech_token: Optional[int] = None, repetition_penalty: float = 1.0,
-                  no_repeat_ngram_size: int = 0, token_logprobs: bool = False) -> PassResult:
+                  no_repeat_ngram_size: int = 0, token_logprobs: bool = False, sequence_bias=None,
+                  bad_words_ids=None) -> PassResult:
         """Beam-search decode (GenerationMixin._beam_search, $TF/generation/utils.py:3208-3512) of W windows with
         num_beams rows each (row = w * num_beams + j, all reading window w's cross-K/V): the prompt as
         decode_pass (language detected from the SOT step when lang_ids is None), then per token one decoder step
@@ -1493,7 +1540,8 @@ class WhisperEngine:
                 res = self.beam_pass(W, num_beams, tail, lang_ids, max_new, use_timestamps, check_every, length_penalty,
                                      enc_row0, r_enc, prefix, enc_rows=enc_rows, criteria=criteria,
                                      no_speech_token=no_speech_token, repetition_penalty=repetition_penalty,
-                                     no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs)
+                                     no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs,
+                                     sequence_bias=sequence_bias, bad_words_ids=bad_words_ids)
                 bb = self._beam
                 nb, st = num_beams, self.gen.special
                 lens = [len(t) for t in res.tokens]  # generated tokens, EOS included (beam_indices' entries)
@@ -1544,7 +1592,8 @@ class WhisperEngine:
             # (a window's history prefix on each of its beam rows too)
             self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail,
                              None if lang_ids is None else [int(x) for x in lang_ids for _ in range(nb)],
-                             None if prefix is None else ([prefix[0][w] for w in range(W) for _ in range(nb)], None))
+                             None if prefix is None else ([prefix[0][w] for w in range(W) for _ in range(nb)], None),
+                             sequence_bias, bad_words_ids)
             self.state[:R].zero_()
             self.state[:R, _lib.TW_ST_LAST:_lib.TW_ST_LASTTS + 1] = -1
             self.pos[:R] = base
@@ -1727,7 +1776,7 @@ class WhisperEngine:
                  prompt_ids: Optional[Sequence[int]] = None,
                  prompt_condition_type: Optional[str] = None, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, length_penalty: float = 1.0,
-                 token_logprobs: bool = False) -> List[List[int]]:
+                 token_logprobs: bool = False, sequence_bias=None, bad_words_ids=None) -> List[List[int]]:
         """Whisper short-form generate() over feats[slot][:n_chunks] (each 3000 frames): language
         detection, the seek loop and segment extraction, returning for every chunk the concatenated
         segment tokens (what generate() returns before padding).
@@ -1747,6 +1796,10 @@ class WhisperEngine:
         SOT step alone, before any prompt (detect_language); the prompt is not part of the returned tokens.
         repetition_penalty / no_repeat_ngram_size: generate()'s history processors on every pass (each seek pass
         starts a new history: its prompt + what it generated); length_penalty: beam search's exponent.
+        sequence_bias (a dict {tuple of ids: float} or a list of [ids, float]) / bad_words_ids (a list of id lists):
+        generate()'s SequenceBiasLogitsProcessor in front of those two and NoBadWordsLogitsProcessor behind them, on
+        the same history, in the same launch (tw_logits_history_bias); checked as transformers checks them, before
+        any work is queued.
         token_logprobs: every pass also records each generated token's log-probability under the step's processed
         scores (output_scores: after the history and Whisper processors and the warpers, at temperature 1 — the terms
         of _retrieve_avg_logprobs): last_pass_logprobs parallel to last_passes, last_token_logprobs parallel to the
@@ -1800,13 +1853,19 @@ class WhisperEngine:
             maxf = [N_FRAMES] * n_chunks
         passes = 0
         self.last_pass_prefixes: List[list] = [[] for _ in range(n_chunks)]
+        bias = {}
+        if sequence_bias is not None or bad_words_ids is not None:
+            seqbias.check_limits(  # (the checks raise here, ahead of the first pass)
+                seqbias.sequence_bias_entries(sequence_bias, self.d.vocab) if sequence_bias is not None else [],
+                seqbias.bad_words_entries(bad_words_ids, st.eot, self.d.vocab) if bad_words_ids is not None else [])
+            bias = {"sequence_bias": sequence_bias, "bad_words_ids": bad_words_ids}
         try:
             return self._seek_loop(n_chunks, tail, prompt_len, max_new_tokens, max_new, seek, segs, passes_raw, langs,
                                    tts, maxf, seg_lists, do_cond, prev_sot, condition_on_prev_tokens, max_passes,
                                    pre_encoded, num_beams, word_timestamps, num_frames, fb, return_timestamps,
                                    window_offset, prompt,
                                    hist={"repetition_penalty": float(repetition_penalty or 1.0),
-                                         "no_repeat_ngram_size": int(no_repeat_ngram_size or 0)},
+                                         "no_repeat_ngram_size": int(no_repeat_ngram_size or 0), **bias},
                                    length_penalty=float(1.0 if length_penalty is None else length_penalty),
                                    token_logprobs=bool(token_logprobs))
         finally:

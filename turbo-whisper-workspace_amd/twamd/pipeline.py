@@ -19,7 +19,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import audio, dist
+from . import audio, dist, seqbias
 from .config import PRESETS, GenerationSettings, WhisperDims
 from .engine import WhisperEngine
 from .engine_f32 import WhisperEngineF32
@@ -175,7 +175,7 @@ class TurboTranscriber:
         if "prompt_ids" not in prompt:
             prompt = {}
         fallback = self._fallback_config(gk)
-        hist = self._history_options(gk)
+        hist = self._history_options(gk, vocab=getattr(getattr(self.engine, "d", None), "vocab", None))
         if gk:
             raise ValueError(f"generate_kwargs not supported by this engine: {sorted(gk)}")
         st = self.gen.special
@@ -401,11 +401,17 @@ class TurboTranscriber:
         return out
 
     @staticmethod
-    def _history_options(gk: Dict[str, Any]) -> Dict[str, Any]:
-        """Pops generate()'s `repetition_penalty`, `no_repeat_ngram_size` and `length_penalty`; returns those that
-        are on as WhisperEngine.generate's kwargs (None, 1.0 and 0 mean off, as _get_logits_processor reads them).
-        Values are checked as RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor check them
-        (generation/logits_process.py), with their messages."""
+    def _history_options(gk: Dict[str, Any], vocab: Optional[int] = None) -> Dict[str, Any]:
+        """Pops generate()'s `repetition_penalty`, `no_repeat_ngram_size`, `length_penalty` and `sequence_bias`;
+        returns those that are on as WhisperEngine.generate's kwargs (None, 1.0 and 0 mean off, as
+        _get_logits_processor reads them). Values are checked as RepetitionPenaltyLogitsProcessor /
+        NoRepeatNGramLogitsProcessor / SequenceBiasLogitsProcessor check them (generation/logits_process.py), with
+        their messages. sequence_bias (a dict {tuple of ids: float} or a list of [ids, float]) comes back as a dict in
+        the kernel's table order — 1-id entries first, then the rest, each in the dict's order; vocab: ids at or past
+        it raise as transformers' first processor call does. `bad_words_ids` is left in place: the callable keeps
+        refusing it as an unsupported kwarg (WhisperEngine.generate takes it; through the callable a sequence is
+        forbidden with a sequence_bias of -inf, which yields the same scores: -inf survives the penalty and the
+        n-gram stage unchanged)."""
         out: Dict[str, Any] = {}
         p = gk.pop("repetition_penalty", None)
         if p is not None and p != 1.0:
@@ -420,6 +426,11 @@ class TurboTranscriber:
         lp = gk.pop("length_penalty", None)
         if lp is not None and float(lp) != 1.0:
             out["length_penalty"] = float(lp)
+        sb = gk.pop("sequence_bias", None)
+        if sb is not None:
+            pre = seqbias.sequence_bias_entries(sb, vocab)
+            seqbias.check_limits(pre, [])
+            out["sequence_bias"] = dict(pre)
         return out
 
     def _fallback_config(self, gk: Dict[str, Any]) -> FallbackConfig:
