@@ -19,7 +19,7 @@ import dataclasses
 import gc
 import os
 import time
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -196,6 +196,62 @@ class PassResult:
     token_lp: Optional[List[List[float]]] = None
 
 
+@dataclasses.dataclass(frozen=True)
+class DecodeOptions:
+    """The per-pass decode options, checked and normalised once (make); generate(), run_batches() and the three
+    passes take make's keywords, below them only the record travels.
+
+    repetition_penalty / no_repeat_ngram_size: generate()'s RepetitionPenaltyLogitsProcessor /
+    NoRepeatNGramLogitsProcessor over the pass's prompt + generated tokens, ahead of every token selection
+    (tw_logits_history_bias; on beam rows with to_logprobs: log_softmax first, tw_beam_step then takes the scores as
+    they are). A sampled pass's log-probabilities are then the penalised scores' (generate()'s output_scores).
+    sequence_bias (a dict {tuple of ids: float} or a list of [ids, float]) / bad_words_ids (a list of id lists):
+    SequenceBiasLogitsProcessor in front of those two and NoBadWordsLogitsProcessor behind them, on the same
+    history, in the same launch; kept as the checked entries pre / post in table order (twamd.seqbias, with
+    transformers' checks and messages).
+    length_penalty: beam search's exponent.
+    token_logprobs: every generated token's log-probability under the step's processed scores (output_scores: after
+    the history and Whisper processors and the warpers, at temperature 1 — the terms of _retrieve_avg_logprobs) in
+    PassResult.token_lp: tw_token_logprob in front of every greedy selection, tw_logits_sample_lp's and
+    tw_beam_step's per-token outputs (the terms of the sums those two return)."""
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    length_penalty: float = 1.0
+    token_logprobs: bool = False
+    pre: Tuple[seqbias.Entry, ...] = ()
+    post: Tuple[seqbias.Entry, ...] = ()
+
+    @classmethod
+    def make(cls, vocab: Optional[int] = None, eos: Optional[int] = None, *, repetition_penalty=None,
+             no_repeat_ngram_size=None, length_penalty=None, token_logprobs=None, sequence_bias=None,
+             bad_words_ids=None) -> "DecodeOptions":
+        """From the public keywords; None is the neutral value. vocab / eos: the model's, for the entry checks."""
+        pre = seqbias.sequence_bias_entries(sequence_bias, vocab) if sequence_bias is not None else []
+        post = seqbias.bad_words_entries(bad_words_ids, eos, vocab) if bad_words_ids is not None else []
+        seqbias.check_limits(pre, post)
+        return cls(float(repetition_penalty or 1.0), int(no_repeat_ngram_size or 0),
+                   float(1.0 if length_penalty is None else length_penalty), bool(token_logprobs), tuple(pre),
+                   tuple(post))
+
+    @property
+    def history(self) -> bool:
+        """A history pre-pass runs ahead of every selection."""
+        return self.repetition_penalty != 1.0 or self.no_repeat_ngram_size != 0 or bool(self.pre or self.post)
+
+    @property
+    def hist_key(self) -> tuple:
+        """What the pre-pass launch takes by value: (penalty, n-gram size, n_pre, n_post)."""
+        return self.repetition_penalty, self.no_repeat_ngram_size, len(self.pre), len(self.post)
+
+    @property
+    def graph_key(self) -> tuple:
+        """What a captured step bakes in: the history key and whether tw_token_logprob runs."""
+        return self.hist_key + (self.token_logprobs,)
+
+
+NO_OPTIONS = DecodeOptions()
+
+
 class WhisperEngine:
     def __init__(self, weights: PackedWeights, gen: GenerationSettings, max_batch: int = 24,
                  device: str = "cuda", use_graphs: bool = True, max_beams: int = 1,
@@ -291,10 +347,11 @@ class WhisperEngine:
         self.sel_ws = torch.empty(B, _lib.TW_SELECT_WS_PER_ROW, dtype=f32, device=dev)
         self.state = torch.zeros(B, _lib.TW_STATE_STRIDE, dtype=i32, device=dev)
         self.tokens = torch.zeros(B, T, dtype=i32, device=dev)
-        # token_logprobs: the generated tokens' log-probabilities (tw_token_logprob / tw_logits_sample_lp / tw_beam_step);
-        # _tlp: the pass in progress asked for them (part of the captured graphs' keys)
+        # token_logprobs: the generated tokens' log-probabilities (tw_token_logprob / tw_logits_sample_lp / tw_beam_step)
         self.token_lp = torch.zeros(B, T, dtype=f32, device=dev)
-        self._tlp = False
+        # the options of the pass in progress (_pass; NO_OPTIONS between passes): their graph_key is part of every
+        # captured graph's key
+        self._opts = NO_OPTIONS
         self.ids = torch.zeros(B, dtype=i32, device=dev)
         self.pos = torch.zeros(B, dtype=i32, device=dev)
         self.row_map = torch.zeros(max_batch, dtype=i32, device=dev)
@@ -309,16 +366,14 @@ class WhisperEngine:
         # prefix; while _masked, the self-attention masks those positions (tw_attn_decode_self_masked)
         self._kv_start = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)
         self._masked = False
-        # repetition_penalty / no_repeat_ngram_size (tw_logits_history ahead of every token selection): per row the
+        # the history pre-pass (tw_logits_history_bias ahead of every token selection, when _opts.history): per row the
         # decoder_input_ids its pass started from (prompt or previous segments with their left pads, SOT, language —
-        # TW_HIST_LANG where the pass detects it —, task, <|notimestamps|>) and their count; _hist = the current
-        # pass's (penalty, n-gram size), None when both are off (no launch, and the value every graph key carries)
+        # TW_HIST_LANG where the pass detects it —, task, <|notimestamps|>) and their count
         self._hist_prefix = torch.zeros(self.max_rows, T, dtype=i32, device=dev)
         self._hist_len = torch.zeros(self.max_rows, dtype=i32, device=dev)
-        self._hist: Optional[tuple] = None
-        # sequence_bias / bad_words_ids (tw_logits_history_bias): the entry table, sized to the kernel's limits so that
-        # the addresses captured graphs hold never change; a pass rewrites the contents (_bias_key: what they hold now)
-        # and the counts, captured by value, ride in _hist and with it in every graph key
+        # sequence_bias / bad_words_ids: the entry table, sized to the kernel's limits so that the addresses captured
+        # graphs hold never change; a pass rewrites the contents (_bias_key: the entries they hold now), and the
+        # counts, captured by value, are in the options' hist_key
         self._bias_ids = torch.zeros(_lib.TW_SEQBIAS_MAX_ENTRIES, _lib.TW_SEQBIAS_MAX_IDS, dtype=i32, device=dev)
         self._bias_len = torch.zeros(_lib.TW_SEQBIAS_MAX_ENTRIES, dtype=i32, device=dev)
         self._bias_val = torch.zeros(_lib.TW_SEQBIAS_MAX_ENTRIES, dtype=torch.float32, device=dev)
@@ -885,12 +940,10 @@ class WhisperEngine:
         perm = [order.index((l, h)) for l, h in heads]
         self._align = {"layers": layers, "n_slots": slot, "pos0": pos0, "n_steps": n_steps, "buf": buf, "perm": perm}
 
-    def _align_weights(self, R: int, n_rows: int) -> np.ndarray:
-        """f32 [R][alignment heads][n_rows][S] of the generated tokens fed so far (steps 0 .. n_rows-1)."""
+    def _align_key(self) -> Optional[tuple]:
+        """What a graph captured during an alignment pass bakes into the probability-recording kernel."""
         al = self._align
-        b = al["buf"][: R * al["n_steps"] * al["n_slots"] * S_ENC].view(R, al["n_steps"], al["n_slots"], S_ENC)
-        w = b[:, :n_rows].permute(0, 2, 1, 3)[:, al["perm"]].float().cpu().numpy()
-        return w
+        return None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr())
 
     def _cross_ptrs(self, li: int, xkv_stride: int, v: DecView):
         """This layer's [k|v][r_enc][H][S][64] block and the row map for the view's rows: identity rows start at
@@ -927,7 +980,7 @@ class WhisperEngine:
         v = v or self._view(0, R)
         if params.mode == 0:  # (language detection sees the raw logits)
             self._history(v.r0, R, v.stream)
-            if self._tlp:  # the log-probability of the token the selection below commits (state still unchanged)
+            if self._opts.token_logprobs:  # the log-probability of the token the selection below commits (state still unchanged)
                 _lib.call("tw_token_logprob", v.logits.data_ptr(), R, self.d.vocab, self.suppress_bits.data_ptr(),
                           ctypes.byref(params), v.state.data_ptr(), self.token_lp[v.r0:].data_ptr(),
                           self.token_lp.stride(0), v.stream.cuda_stream)
@@ -944,19 +997,17 @@ class WhisperEngine:
                   ctypes.byref(params), v.state.data_ptr(), v.tokens.data_ptr() if tokens else None,
                   v.tokens.shape[1], v.ids.data_ptr(), v.pos.data_ptr(), v.sel_ws.data_ptr(), v.stream.cuda_stream)
 
-    def _bias_begin(self, sequence_bias, bad_words_ids) -> tuple:
-        """Checks the pass's sequence_bias / bad_words_ids (transformers' checks and messages, twamd.seqbias), writes
-        them to the table buffers in the kernel's order when those hold something else, and returns
-        (n_pre, n_post)."""
-        if sequence_bias is None and bad_words_ids is None:
-            return 0, 0
-        V = self.d.vocab
-        pre = seqbias.sequence_bias_entries(sequence_bias, V) if sequence_bias is not None else []
-        post = seqbias.bad_words_entries(bad_words_ids, self.gen.special.eot, V) if bad_words_ids is not None else []
-        seqbias.check_limits(pre, post)
-        entries = pre + post
-        key = tuple(entries)
-        if entries and key != self._bias_key:
+    def _hist_begin(self, R: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]], prefix_rows=None) -> None:
+        """Start the pass's token history when its options run the pre-pass: rows [0, R) of the prefix buffer take
+        what transformers hands its processors as decoder_input_ids before the first generated token — the pass's
+        prefix rows (prompt_ids / conditioned previous segments, left pads included), <|startoftranscript|>, the
+        language (TW_HIST_LANG when the pass detects it: the kernel reads state[r][TW_ST_LANG]) and the tail — and
+        the table buffers the options' entries in the kernel's order, when they hold something else."""
+        opts = self._opts
+        if not opts.history:
+            return
+        entries = opts.pre + opts.post
+        if entries and entries != self._bias_key:
             n = len(entries)
             ids = np.zeros((n, _lib.TW_SEQBIAS_MAX_IDS), np.int32)
             for e, (seq, _) in enumerate(entries):
@@ -965,26 +1016,11 @@ class WhisperEngine:
             self._bias_ids[:n] = torch.from_numpy(ids).to(self.device)
             self._bias_len[:n] = torch.tensor([len(seq) for seq, _ in entries], dtype=torch.int32, device=self.device)
             self._bias_val[:n] = torch.tensor([b for _, b in entries], dtype=torch.float32, device=self.device)
-            self._bias_key = key
-        return len(pre), len(post)
-
-    def _hist_begin(self, R: int, repetition_penalty: float, no_repeat_ngram_size: int, tail: Sequence[int],
-                    lang_ids: Optional[Sequence[int]], prefix=None, sequence_bias=None, bad_words_ids=None) -> None:
-        """Start a pass's token history for tw_logits_history: rows [0, R) of the prefix buffer take what
-        transformers hands its processors as decoder_input_ids before the first generated token — the pass's prefix
-        rows (prompt_ids / conditioned previous segments, left pads included), <|startoftranscript|>, the language
-        (TW_HIST_LANG when the pass detects it: the kernel reads state[r][TW_ST_LANG]) and the tail. With every
-        option off nothing is copied and no pre-pass is launched (_hist None). sequence_bias / bad_words_ids: the
-        pass's entry table (_bias_begin); _hist then also carries its two counts."""
-        p, n = float(repetition_penalty or 1.0), int(no_repeat_ngram_size or 0)
-        n_pre, n_post = self._bias_begin(sequence_bias, bad_words_ids)
-        if p == 1.0 and n == 0 and n_pre + n_post == 0:
-            self._hist = None
-            return
+            self._bias_key = entries
         st = self.gen.special
         rows = []
         for r in range(R):
-            h = [int(t) for t in prefix[0][r]] if prefix is not None and prefix[0] else []
+            h = [int(t) for t in prefix_rows[r]] if prefix_rows else []
             h.append(st.sot)
             if st.is_multilingual:
                 h.append(_lib.TW_HIST_LANG if lang_ids is None else int(lang_ids[r]))
@@ -995,24 +1031,21 @@ class WhisperEngine:
             raise ValueError(f"decoder prompt of {L} tokens exceeds {self._hist_prefix.shape[1]} positions")
         self._hist_prefix[:R, :L] = torch.as_tensor(rows, dtype=torch.int32, device=self.device)
         self._hist_len[:R] = L
-        self._hist = (p, n, n_pre, n_post) if n_pre + n_post else (p, n)
 
     def _history(self, r0: int, R: int, stream, to_logprobs: bool = False) -> None:
-        """The history processors (repetition penalty, no-repeat n-gram) on the logits of rows [r0, r0 + R), in
-        place, when the pass set them (tw_logits_history; to_logprobs: beam rows, log_softmax first). With a
-        sequence_bias / bad_words_ids table the same launch also runs those two stages (tw_logits_history_bias)."""
-        if self._hist is None:
+        """The history pre-pass on the logits of rows [r0, r0 + R), in place, when the pass's options run it
+        (DecodeOptions.history; to_logprobs: beam rows, log_softmax first). Without entries the table is null."""
+        opts = self._opts
+        if not opts.history:
             return
-        p, n = self._hist[:2]
-        args = (self.logits[r0:].data_ptr(), R, self.logits.stride(0), self.d.vocab,
-                self._hist_prefix[r0:].data_ptr(), self._hist_prefix.stride(0), self._hist_len[r0:].data_ptr(),
-                self.tokens[r0:].data_ptr(), self.tokens.stride(0), self.state[r0:].data_ptr(), p, n, int(to_logprobs))
-        if len(self._hist) == 2:
-            _lib.call("tw_logits_history", *args, stream.cuda_stream)
-            return
-        table = _lib.TwSeqBias(self._bias_ids.data_ptr(), self._bias_len.data_ptr(), self._bias_val.data_ptr(),
-                               self._bias_ids.stride(0), self._hist[2], self._hist[3])
-        _lib.call("tw_logits_history_bias", *args, ctypes.byref(table), stream.cuda_stream)
+        p, n, n_pre, n_post = opts.hist_key
+        table = (ctypes.byref(_lib.TwSeqBias(self._bias_ids.data_ptr(), self._bias_len.data_ptr(),
+                                             self._bias_val.data_ptr(), self._bias_ids.stride(0), n_pre, n_post))
+                 if n_pre + n_post else None)
+        _lib.call("tw_logits_history_bias", self.logits[r0:].data_ptr(), R, self.logits.stride(0), self.d.vocab,
+                  self._hist_prefix[r0:].data_ptr(), self._hist_prefix.stride(0), self._hist_len[r0:].data_ptr(),
+                  self.tokens[r0:].data_ptr(), self.tokens.stride(0), self.state[r0:].data_ptr(), p, n,
+                  int(to_logprobs), table, stream.cuda_stream)
 
     # Teacher-forcing hook of decode_pass (parity harness, tests/test_gpu_turbo.py and bench.py's parity leg):
     # hook(k, view) runs on the host after the step that produced generated position k (view None: the prompt's last
@@ -1141,18 +1174,31 @@ class WhisperEngine:
         L = len(prefix[0][0]) if prefix is not None and prefix[0] else 0
         return L + 1 + (1 if self.gen.special.is_multilingual else 0) + len(tail)
 
-    def _token_ts(self, R: int, P: int, res: PassResult, num_frames: Optional[Sequence[int]]) -> None:
-        """res.token_ts from the alignment heads' probabilities of a greedy / sampled pass (self._align): the pass's
-        rows standardised over its padded length (max generated - 1 fed tokens), as _extract_token_timestamps does
-        over the batch (generation_whisper.py:241-381); prompt positions 0."""
-        st = self.gen.special
-        real = [(t.index(st.eot) + 1) if st.eot in t else len(t) for t in res.tokens]
-        rows = max(real) - 1 if real else 0
-        w = self._align_weights(R, rows) if rows > 0 else None
+    def _token_ts(self, res: PassResult, num_frames: Optional[Sequence[int]], nb: int = 1) -> None:
+        """res.token_ts from the alignment heads' probabilities the pass recorded (self._align): its sequences
+        standardised over their padded length (max generated - 1 fed tokens), as _extract_token_timestamps does over
+        the batch (generation_whisper.py:241-381); prompt positions 0. nb > 1: a beam pass' windows, each from the
+        rows that fed its best hypothesis (the kernel's fin_tab: generate's beam_indices, :265-300; past a
+        hypothesis' end, row 0's, as index -1 -> 0 there)."""
+        al, eot, n = self._align, self.gen.special.eot, len(res.tokens)
+        P = al["pos0"]
+        lens = [(t.index(eot) + 1) if eot in t else len(t) for t in res.tokens]  # generated tokens, EOS included
+        rows = max(lens) - 1 if lens else 0
+        if rows > 0:
+            b = al["buf"][: n * nb * al["n_steps"] * al["n_slots"] * S_ENC].view(n * nb, al["n_steps"], al["n_slots"],
+                                                                                 S_ENC)
+            if nb == 1:
+                w = b[:, :rows]
+            else:
+                ftab = self._beam["fin_tab"][: n * nb: nb, P: P + rows].long()  # rows that fed positions P .. P+rows-1
+                i = torch.arange(rows, device=self.device)
+                ftab = torch.where(i[None, :] + 1 < torch.tensor(lens, device=self.device)[:, None], ftab, 0)
+                w = b[ftab, i[None, :]]
+            w = w.permute(0, 2, 1, 3)[:, al["perm"]].float().cpu().numpy()  # [n][alignment heads][rows][S]
         res.token_ts = []
-        for r in range(R):
+        for r in range(n):
             nf = None if num_frames is None else int(num_frames[r])
-            ts = (alignment.token_timestamps(w[r], 0, nf, self.gen.median_filter_width) if w is not None
+            ts = (alignment.token_timestamps(w[r], 0, nf, self.gen.median_filter_width) if rows > 0
                   else np.zeros(1, np.float32))
             res.token_ts.append(np.concatenate([np.zeros(P, np.float32), ts]))
 
@@ -1160,8 +1206,7 @@ class WhisperEngine:
         """condition_on_prev_tokens: feed a pass's left-padded prefix (per row [<|startofprev|>] + the previous
         segments' tokens, generation_whisper.py:1853-1918) at positions 0 .. L-1 ahead of the init tokens; returns L.
         prefix = (rows [R][L], pads [R]). The pad positions are fed too (transformers' cache positions count them) and
-        masked out of every later query (kv_start, tw_attn_decode_self_masked); the caller ends the pass with
-        _masked = False."""
+        masked out of every later query (kv_start, tw_attn_decode_self_masked) until the pass ends (_pass)."""
         if prefix is None:
             return 0
         rows, pads = prefix
@@ -1179,6 +1224,71 @@ class WhisperEngine:
             self.pos[:R] = k
             self.decoder_step(R, with_logits=False, r_enc=r_enc)
         return L
+
+    def _options(self, opts: Optional[DecodeOptions], kw: dict) -> DecodeOptions:
+        """A pass's options: the record (a caller inside the engine), else from DecodeOptions.make's keywords."""
+        if opts is None:
+            return DecodeOptions.make(self.d.vocab, self.gen.special.eot, **kw)
+        if kw:
+            raise TypeError(f"keywords beside opts: {sorted(kw)}")
+        return opts
+
+    @contextlib.contextmanager
+    def _pass(self, opts: DecodeOptions, align: Optional[tuple] = None, row_map: Optional[torch.Tensor] = None,
+              row_group: int = 1, kv_tab: Optional[torch.Tensor] = None):
+        """The engine state one decode pass runs under: its options, the alignment heads' recording (align =
+        (rows, first position, steps) of _align_setup), the decoder rows' encoder rows (row_map -> dec_row_map;
+        row_group consecutive rows share one), beam search's K/V position table, and the prompt mask _prefill sets.
+        All of it is back at its idle value when the pass ends, however it ends."""
+        try:
+            self._opts = opts
+            if align is not None:
+                self._align_setup(*align)
+            if row_map is not None:
+                self.dec_row_map[: row_map.numel()] = row_map
+                self._use_dec_row_map = True
+            self._row_group, self._kv_tab = row_group, kv_tab
+            yield
+        finally:
+            self._opts, self._align, self._masked = NO_OPTIONS, None, False
+            self._use_dec_row_map, self._row_group, self._kv_tab = False, 1, None
+
+    def _prompt_phase(self, R: int, r_enc: int, base: int, lang_ids: Optional[Sequence[int]], tail: Sequence[int],
+                      max_new: int, no_speech_token: Optional[int] = None) -> bool:
+        """State reset and the prompt [SOT, (lang), *tail] fed one token per step from position base, up to its last
+        token (ids / pos hold it: the pass's first generation step feeds it). lang_ids None on a multilingual model:
+        the language is the mode-1 selection from the SOT step's logits. no_speech_token: WhisperNoSpeechDetection's
+        probability of it from the same logits (state[TW_ST_NOSPEECH]); returns whether that is still owed (a bare
+        SOT prompt: its step is the first generation step). Nothing here waits for the device, and only per-row
+        lang_ids are copied to it (decode_pass captures this phase otherwise)."""
+        st = self.gen.special
+        self.state[:R].zero_()
+        self.state[:R, _lib.TW_ST_LAST:_lib.TW_ST_LASTTS + 1] = -1
+        self.pos[:R] = base
+        self.ids[:R] = st.sot
+        rest: List = []  # per-position token ids after SOT (int, or per-row list; None: detected)
+        if st.is_multilingual:
+            rest.append(None if lang_ids is None else [int(x) for x in lang_ids])
+        rest.extend(int(t) for t in tail)
+        for k, tok in enumerate(rest):
+            self.decoder_step(R, with_logits=k == 0 and (tok is None or no_speech_token is not None), r_enc=r_enc)
+            if k == 0:
+                self._no_speech(R, no_speech_token)
+            if tok is None:
+                self._select(R, self._select_params(1, max_new), tokens=False)  # ids <- lang, pos += 1
+                continue
+            if isinstance(tok, list):
+                self.ids[:R] = torch.as_tensor(tok, dtype=torch.int32, device=self.device)
+            else:
+                self.ids[:R] = tok
+            self.pos[:R] = base + k + 1
+        return not rest and no_speech_token is not None
+
+    def _no_speech(self, R: int, token: Optional[int]) -> None:
+        """state[TW_ST_NOSPEECH] of rows [0, R) from the logits in place (those of the <|startoftranscript|> step)."""
+        if token is not None:
+            V = self.d.vocab
+            _lib.call("tw_token_prob", self.logits.data_ptr(), R, V, V, int(token), self.state.data_ptr(), self._s)
 
     @on_engine_streams
     def _detect_languages(self, R: int) -> List[int]:
@@ -1201,95 +1311,64 @@ class WhisperEngine:
     @on_engine_streams
     def decode_pass(self, R: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]], max_new: int,
                     check_every: int = 8, use_timestamps: bool = True, align: bool = False,
-                    num_frames: Optional[Sequence[int]] = None, prefix=None, repetition_penalty: float = 1.0,
-                    no_repeat_ngram_size: int = 0, token_logprobs: bool = False, sequence_bias=None,
-                    bad_words_ids=None) -> PassResult:
+                    num_frames: Optional[Sequence[int]] = None, prefix=None, opts: Optional[DecodeOptions] = None,
+                    **options) -> PassResult:
         """Greedy decode of R rows from the prompt [SOT, (lang), *tail] (the init tokens of
         _retrieve_init_tokens; the language is detected from the SOT step when lang_ids is None on a
         multilingual model). Returns the generated tokens of every row; with align, also every row's token-level
         timestamps (alignment-head cross-attention of the fed tokens -> DTW; num_frames: the rows' valid frames
-        minus their seek, as generate() passes them). repetition_penalty / no_repeat_ngram_size: generate()'s
-        RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor over prompt + generated tokens, ahead of every
-        selection (tw_logits_history). token_logprobs: also every generated token's log-probability under the step's
-        processed scores (PassResult.token_lp), from tw_token_logprob in front of every selection."""
-        if align:
-            P = self._prompt_len(tail, prefix)
-            self._align_setup(R, P, max_new)
-            try:
-                res = self.decode_pass(R, tail, lang_ids, max_new, check_every, use_timestamps, prefix=prefix,
-                                       repetition_penalty=repetition_penalty,
-                                       no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs,
-                                       sequence_bias=sequence_bias, bad_words_ids=bad_words_ids)
-                self._token_ts(R, P, res, num_frames)
-                return res
-            finally:
-                self._align = None
-        if token_logprobs:
-            self._tlp = True
-            try:
-                res = self.decode_pass(R, tail, lang_ids, max_new, check_every, use_timestamps, prefix=prefix,
-                                       repetition_penalty=repetition_penalty,
-                                       no_repeat_ngram_size=no_repeat_ngram_size,
-                                       sequence_bias=sequence_bias, bad_words_ids=bad_words_ids)
-            finally:
-                self._tlp = False
-            lp = self.token_lp[:R].tolist()
-            res.token_lp = [lp[r][: len(res.tokens[r])] for r in range(R)]
-            return res
+        minus their seek, as generate() passes them). options: DecodeOptions.make's keywords."""
+        opts = self._options(opts, options)
         st = self.gen.special
-        dev = self.device
-        self._dec_context()
-        self.stream.wait_event(self._enc_ev[self._slot])  # the cross-K/V of this slot is written
         detect = st.is_multilingual and lang_ids is None
-        params = self._select_params(0, max_new, use_timestamps)
-        base = self._prefill(R, prefix)  # (condition_on_prev_tokens: the init tokens start at position base)
-        self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail, lang_ids, prefix, sequence_bias,
-                         bad_words_ids)
+        with self._pass(opts, align=(R, self._prompt_len(tail, prefix), max_new) if align else None):
+            self._dec_context()
+            self.stream.wait_event(self._enc_ev[self._slot])  # the cross-K/V of this slot is written
+            params = self._select_params(0, max_new, use_timestamps)
+            base = self._prefill(R, prefix)  # (condition_on_prev_tokens: the init tokens start at position base)
+            self._hist_begin(R, tail, lang_ids, prefix and prefix[0])
 
-        def prompt() -> None:
-            """State reset, the prompt steps [SOT, (lang), *tail] and the first generated token (one token per
-            step; the language detected from the SOT step's logits by the mode-1 selection when lang_ids is None)."""
-            self.state[:R].zero_()
-            self.state[:R, _lib.TW_ST_LAST:_lib.TW_ST_LASTTS + 1] = -1
-            self.pos[:R] = base
-            self.ids[:R] = st.sot
-            prompt_rest: List = []  # per-position token ids after SOT (int, or per-row list)
-            if st.is_multilingual:
-                prompt_rest.append(None if lang_ids is None else list(lang_ids))
-            prompt_rest.extend(int(t) for t in tail)
-            for k, tok in enumerate(prompt_rest):
-                if k == 0 and detect:
-                    self.decoder_step(R)
-                    self._select(R, self._select_params(1, max_new), tokens=False)  # ids <- lang, pos += 1
-                    continue
-                self.decoder_step(R, with_logits=False)
-                if isinstance(tok, list):
-                    self.ids[:R] = torch.as_tensor(tok, dtype=torch.int32, device=dev)
-                else:
-                    self.ids[:R] = tok
-                self.pos[:R] = base + k + 1
-            self._gen_step(R, params)  # last prompt token -> first generated token
+            def prompt() -> None:  # the prompt steps and the first generated token (from the last prompt token)
+                self._prompt_phase(R, R, base, lang_ids, tail, max_new)
+                self._gen_step(R, params)
 
-        # the prompt phase as one captured graph (its ~140 launches replayed instead of issued one by one from the
-        # host while the next batch's encoder keeps the GPU busy); per-row language ids given by the caller stay eager
-        # (their host-to-device copy is not capturable)
-        if self.use_graphs and self.prompt_graph and (detect or not st.is_multilingual) and not base:
-            al = self._align  # (keyed like _graph_for: an alignment pass captures the probability-recording kernel)
-            key = ("prompt", R, tuple(int(t) for t in tail), max_new, use_timestamps, self._slot,
-                   None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()), self._dec_ctx,
-                   self._hist, self._tlp)
-            g = self._graphs.get(key)
-            if g is None:
-                g = torch.cuda.CUDAGraph()
-                with _capture(g, self.stream):  # records, does not execute
-                    prompt()
-                self._graphs[key] = g
-            g.replay()
-        else:
-            prompt()
+            # the prompt phase as one captured graph (its ~140 launches replayed instead of issued one by one from
+            # the host while the next batch's encoder keeps the GPU busy); per-row language ids given by the caller
+            # stay eager (their host-to-device copy is not capturable)
+            if self.use_graphs and self.prompt_graph and (detect or not st.is_multilingual) and not base:
+                # (keyed like _graph_for: an alignment pass captures the probability-recording kernel)
+                key = ("prompt", R, tuple(int(t) for t in tail), max_new, use_timestamps, self._slot,
+                       self._align_key(), self._dec_ctx, opts.graph_key)
+                g = self._graphs.get(key)
+                if g is None:
+                    g = torch.cuda.CUDAGraph()
+                    with _capture(g, self.stream):  # records, does not execute
+                        prompt()
+                    self._graphs[key] = g
+                g.replay()
+            else:
+                prompt()
+            self._chain_loop(R, params, max_new, check_every)
+            ngen = self.state[:R, _lib.TW_ST_NGEN].tolist()
+            toks = self.tokens[:R].tolist()
+            if self._dec_ctx[2]:
+                self.check_fused()
+            # (the mode-1 selection alone writes TW_ST_LANG)
+            res = PassResult([toks[r][: ngen[r]] for r in range(R)],
+                             self.state[:R, _lib.TW_ST_LANG].tolist() if detect else
+                             None if lang_ids is None else list(lang_ids))
+            if opts.token_logprobs:
+                lp = self.token_lp[:R].tolist()
+                res.token_lp = [lp[r][: ngen[r]] for r in range(R)]
+            if align:
+                self._token_ts(res, num_frames)
+        return res
+
+    def _chain_loop(self, R: int, params, max_new: int, check_every: int) -> None:
+        """decode_pass's generation steps after the first: the rows split into chains on their own high-priority
+        streams, each replaying its captured decode step (the chains' latency-bound kernels run concurrently), until
+        every row has finished (checked every check_every steps) or max_new tokens are out."""
         steps = 1
-        # generation loop: the rows split into chains on their own high-priority streams, each replaying its
-        # captured decode step; the chains' latency-bound kernels run concurrently
         chains = self._chains(R)
         fused = self.fused_select
         graphs = ([self._graph_for(R, params, i, c, fused) for i, c in enumerate(chains)] if self.use_graphs
@@ -1368,124 +1447,69 @@ class WhisperEngine:
             ev1 = torch.cuda.Event(enable_timing=True)
             ev1.record(self.stream)
             self.pass_events.append((ev0, ev1, steps - 1, time.perf_counter() - th0))
-        ngen = self.state[:R, _lib.TW_ST_NGEN].tolist()
-        toks = self.tokens[:R].tolist()
-        if self._dec_ctx[2]:
-            self.check_fused()
-        detected = self.state[:R, _lib.TW_ST_LANG].tolist() if detect else None  # (mode-1 selection only writes it)
-        return PassResult([toks[r][: ngen[r]] for r in range(R)], detected if lang_ids is None else list(lang_ids))
 
     @on_engine_streams
     def sample_pass(self, R: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]], max_new: int,
                     temperature: float = 0.0, top_k: int = 50, seed: int = 0, row_keys: Optional[Sequence[int]] = None,
                     use_timestamps: bool = True, enc_rows: Optional[Sequence[int]] = None, r_enc: Optional[int] = None,
                     no_speech_token: Optional[int] = None, check_every: int = 8, prefix=None, align: bool = False,
-                    num_frames: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
-                    no_repeat_ngram_size: int = 0, token_logprobs: bool = False, sequence_bias=None,
-                    bad_words_ids=None) -> PassResult:
+                    num_frames: Optional[Sequence[int]] = None, opts: Optional[DecodeOptions] = None,
+                    **options) -> PassResult:
         """One decode pass of the temperature-fallback loop (WhisperGenerationMixin.generate_with_fallback,
-        generation_whisper.py:970-1116), eager, one tw_logits_sample per token: greedy when temperature == 0
+        generation_whisper.py:970-1116), eager, one tw_logits_sample_lp per token: greedy when temperature == 0
         (the tokens of decode_pass), else a draw from softmax(processed / T) over the top_k scores. Per row it also
         returns the sum of the chosen tokens' log-probabilities (the avg_logprob criterion's numerator) and, with
         no_speech_token, WhisperNoSpeechDetection's probability of it at the SOT position. enc_rows: the encoder
         rows (of the r_enc-row encoded batch in this slot) the R decoder rows read (default 0..R-1). align: also the
-        rows' token-level timestamps (as decode_pass). repetition_penalty / no_repeat_ngram_size as decode_pass: the
-        log-probability is then the penalised scores' (generate()'s output_scores). token_logprobs: also the terms of
-        that sum, one per generated token (PassResult.token_lp, tw_logits_sample_lp)."""
-        if align:
-            P = self._prompt_len(tail, prefix)
-            self._align_setup(R, P, max_new)
-            try:
-                res = self.sample_pass(R, tail, lang_ids, max_new, temperature, top_k, seed, row_keys, use_timestamps,
-                                       enc_rows, r_enc, no_speech_token, check_every, prefix,
-                                       repetition_penalty=repetition_penalty,
-                                       no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs,
-                                       sequence_bias=sequence_bias, bad_words_ids=bad_words_ids)
-                self._token_ts(R, P, res, num_frames)
-                return res
-            finally:
-                self._align = None
+        rows' token-level timestamps (as decode_pass). options: DecodeOptions.make's keywords."""
+        opts = self._options(opts, options)
         st = self.gen.special
         dev = self.device
         r_enc = R if r_enc is None else r_enc
-        self._dec_context()
-        self.stream.wait_event(self._enc_ev[self._slot])
         detect = st.is_multilingual and lang_ids is None
-        params = self._select_params(0, max_new, use_timestamps)
-        keys = torch.as_tensor(list(row_keys) if row_keys is not None else list(range(R)), dtype=torch.int32,
-                               device=dev)
-        V = self.d.vocab
-        s = self.stream.cuda_stream
-        if enc_rows is not None:
-            self.dec_row_map[:R] = torch.as_tensor(list(enc_rows), dtype=torch.int32, device=dev)
-            self._use_dec_row_map = True
-            self._row_group = 1
-        try:
+        with self._pass(opts, align=(R, self._prompt_len(tail, prefix), max_new) if align else None,
+                        row_map=None if enc_rows is None else torch.as_tensor(list(enc_rows), dtype=torch.int32,
+                                                                              device=dev)):
+            self._dec_context()
+            self.stream.wait_event(self._enc_ev[self._slot])
+            params = self._select_params(0, max_new, use_timestamps)
+            keys = torch.as_tensor(list(row_keys) if row_keys is not None else list(range(R)), dtype=torch.int32,
+                                   device=dev)
             base = self._prefill(R, prefix, r_enc)
-            self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail, lang_ids, prefix, sequence_bias,
-                             bad_words_ids)
-            self.state[:R].zero_()
-            self.state[:R, _lib.TW_ST_LAST:_lib.TW_ST_LASTTS + 1] = -1
-            self.pos[:R] = base
-            self.ids[:R] = st.sot
-            prompt_rest: List = []
-            if st.is_multilingual:
-                prompt_rest.append(None if lang_ids is None else list(lang_ids))
-            prompt_rest.extend(int(t) for t in tail)
-
-            def no_speech() -> None:  # the logits of the step that fed <|startoftranscript|>
-                if no_speech_token is not None:
-                    _lib.call("tw_token_prob", self.logits.data_ptr(), R, V, V, int(no_speech_token),
-                              self.state.data_ptr(), s)
-
-            for k, tok in enumerate(prompt_rest):
-                want = k == 0 and (detect or no_speech_token is not None)
-                self.decoder_step(R, with_logits=want, r_enc=r_enc)
-                if k == 0:
-                    no_speech()
-                if k == 0 and detect:
-                    self._select(R, self._select_params(1, max_new), tokens=False)  # ids <- lang, pos += 1
-                    continue
-                if isinstance(tok, list):
-                    self.ids[:R] = torch.as_tensor(tok, dtype=torch.int32, device=dev)
-                else:
-                    self.ids[:R] = tok
-                self.pos[:R] = base + k + 1
+            self._hist_begin(R, tail, lang_ids, prefix and prefix[0])
+            ns_owed = self._prompt_phase(R, r_enc, base, lang_ids, tail, max_new, no_speech_token)
+            token_lp = self.token_lp if opts.token_logprobs else None
             steps = 0
             while steps < max_new:
                 self.decoder_step(R, r_enc=r_enc)
-                if steps == 0 and not prompt_rest:
-                    no_speech()
+                if steps == 0 and ns_owed:
+                    self._no_speech(R, no_speech_token)
                 self._history(0, R, self.stream)
-                if token_logprobs:
-                    _lib.call("tw_logits_sample_lp", self.logits.data_ptr(), R, V, self.suppress_bits.data_ptr(),
-                              ctypes.byref(params), float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                              keys.data_ptr(), self.state.data_ptr(), self.tokens.data_ptr(), self.tokens.shape[1],
-                              self.ids.data_ptr(), self.pos.data_ptr(), self.token_lp.data_ptr(),
-                              self.token_lp.stride(0), s)
-                else:
-                    _lib.call("tw_logits_sample", self.logits.data_ptr(), R, V, self.suppress_bits.data_ptr(),
-                              ctypes.byref(params), float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                              keys.data_ptr(), self.state.data_ptr(), self.tokens.data_ptr(), self.tokens.shape[1],
-                              self.ids.data_ptr(), self.pos.data_ptr(), s)
+                _lib.call("tw_logits_sample_lp", self.logits.data_ptr(), R, self.d.vocab,
+                          self.suppress_bits.data_ptr(), ctypes.byref(params), float(temperature), int(top_k),
+                          int(seed) & 0xFFFFFFFFFFFFFFFF, keys.data_ptr(), self.state.data_ptr(),
+                          self.tokens.data_ptr(), self.tokens.shape[1], self.ids.data_ptr(), self.pos.data_ptr(),
+                          _lib.ptr(token_lp), 0 if token_lp is None else token_lp.stride(0), self._s)
                 steps += 1
                 if steps % check_every == 0 and bool(self.state[:R, _lib.TW_ST_FINISHED].all().item()):
                     break
             stt = self.state[:R].cpu()
-        finally:
-            self._use_dec_row_map = False
-            self._row_group = 1
-        ngen = stt[:, _lib.TW_ST_NGEN].tolist()
-        toks = self.tokens[:R].tolist()
-        if self._dec_ctx[2]:
-            self.check_fused()
-        f32 = stt.view(torch.float32)
-        lp = self.token_lp[:R].tolist() if token_logprobs else None
-        return PassResult([toks[r][: ngen[r]] for r in range(R)],
-                          stt[:, _lib.TW_ST_LANG].tolist() if detect else list(lang_ids) if lang_ids is not None else None,
-                          sum_logprob=f32[:, _lib.TW_ST_SUMLP].tolist(),
-                          no_speech_prob=f32[:, _lib.TW_ST_NOSPEECH].tolist() if no_speech_token is not None else None,
-                          token_lp=None if lp is None else [lp[r][: ngen[r]] for r in range(R)])
+            ngen = stt[:, _lib.TW_ST_NGEN].tolist()
+            toks = self.tokens[:R].tolist()
+            if self._dec_ctx[2]:
+                self.check_fused()
+            f32 = stt.view(torch.float32)
+            res = PassResult([toks[r][: ngen[r]] for r in range(R)],
+                             stt[:, _lib.TW_ST_LANG].tolist() if detect else
+                             None if lang_ids is None else list(lang_ids),
+                             sum_logprob=f32[:, _lib.TW_ST_SUMLP].tolist(),
+                             no_speech_prob=f32[:, _lib.TW_ST_NOSPEECH].tolist() if no_speech_token is not None else None)
+            if token_lp is not None:
+                lp = token_lp[:R].tolist()
+                res.token_lp = [lp[r][: ngen[r]] for r in range(R)]
+            if align:
+                self._token_ts(res, num_frames)
+        return res
 
     def _beam_buffers(self, R: int) -> dict:
         if self._beam is None or self._beam["rows"] < R:
@@ -1512,57 +1536,24 @@ class WhisperEngine:
 
     @on_engine_streams
     def beam_pass(self, W: int, num_beams: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]], max_new: int,
-                  use_timestamps: bool = True, check_every: int = 8, length_penalty: float = 1.0,
-                  enc_row0: int = 0, r_enc: Optional[int] = None, prefix=None, align: bool = False,
-                  num_frames: Optional[Sequence[int]] = None, enc_rows: Optional[Sequence[int]] = None,
-                  criteria: bool = False, no_speech_token: Optional[int] = None, repetition_penalty: float = 1.0,
-                  no_repeat_ngram_size: int = 0, token_logprobs: bool = False, sequence_bias=None,
-                  bad_words_ids=None) -> PassResult:
+                  use_timestamps: bool = True, check_every: int = 8, enc_row0: int = 0, r_enc: Optional[int] = None,
+                  prefix=None, align: bool = False, num_frames: Optional[Sequence[int]] = None,
+                  enc_rows: Optional[Sequence[int]] = None, criteria: bool = False,
+                  no_speech_token: Optional[int] = None, opts: Optional[DecodeOptions] = None,
+                  **options) -> PassResult:
         """Beam-search decode (GenerationMixin._beam_search, $TF/generation/utils.py:3208-3512) of W windows with
         num_beams rows each (row = w * num_beams + j, all reading window w's cross-K/V): the prompt as
         decode_pass (language detected from the SOT step when lang_ids is None), then per token one decoder step
-        over all rows and tw_beam_step (which also repoints the self-attention K/V position table). Returns the best finished hypothesis of
-        every window (with its EOS when it ended on one). enc_row0 / r_enc: the windows' first row and the batch
-        the cross-K/V slot was encoded with (default 0 / W). align: also every window's token-level timestamps, from
-        the alignment heads' cross-attention of the rows that fed its best hypothesis (the kernel's fin_tab: generate's
-        beam_indices, generation_whisper.py:265-300; past a hypothesis' end, row 0's, as index -1 -> 0 there).
-        enc_rows: each window's encoder row (instead of enc_row0 + w: a fallback round's subset). criteria: also each
-        best hypothesis' sum of log-probabilities renormalised over the allowed tokens (the fallback's average
-        log-probability numerator, tw_beam_step's fin_lp) and, with no_speech_token, WhisperNoSpeechDetection's
-        probability at the <|startoftranscript|> step (PassResult.sum_logprob / no_speech_prob).
-        repetition_penalty / no_repeat_ngram_size: the history processors on every beam's log-probabilities
-        (tw_logits_history with to_logprobs; tw_beam_step then takes the scores as they are). token_logprobs: also the
-        terms of the best hypothesis' renormalised sum, one per token (PassResult.token_lp, tw_beam_step's fin_tlp)."""
-        if align:
-            P = self._prompt_len(tail, prefix)
-            self._align_setup(W * num_beams, P, max_new)
-            try:
-                res = self.beam_pass(W, num_beams, tail, lang_ids, max_new, use_timestamps, check_every, length_penalty,
-                                     enc_row0, r_enc, prefix, enc_rows=enc_rows, criteria=criteria,
-                                     no_speech_token=no_speech_token, repetition_penalty=repetition_penalty,
-                                     no_repeat_ngram_size=no_repeat_ngram_size, token_logprobs=token_logprobs,
-                                     sequence_bias=sequence_bias, bad_words_ids=bad_words_ids)
-                bb = self._beam
-                nb, st = num_beams, self.gen.special
-                lens = [len(t) for t in res.tokens]  # generated tokens, EOS included (beam_indices' entries)
-                rows = max(lens) - 1 if lens else 0
-                res.token_ts = []
-                if rows > 0:
-                    al = self._align
-                    b = al["buf"][: W * nb * al["n_steps"] * al["n_slots"] * S_ENC].view(
-                        W * nb, al["n_steps"], al["n_slots"], S_ENC)
-                    ftab = bb["fin_tab"][: W * nb: nb, P: P + rows].long()  # rows that fed positions P .. P+rows-1
-                    i = torch.arange(rows, device=self.device)
-                    ftab = torch.where(i[None, :] + 1 < torch.tensor(lens, device=self.device)[:, None], ftab, 0)
-                    w = b[ftab, i[None, :]].permute(0, 2, 1, 3)[:, al["perm"]].float().cpu().numpy()
-                for k in range(W):
-                    nf = None if num_frames is None else int(num_frames[k])
-                    ts = (alignment.token_timestamps(w[k], 0, nf, self.gen.median_filter_width) if rows > 0
-                          else np.zeros(1, np.float32))
-                    res.token_ts.append(np.concatenate([np.zeros(P, np.float32), ts]))
-                return res
-            finally:
-                self._align = None
+        over all rows and tw_beam_step (which also repoints the self-attention K/V position table). Returns the best
+        finished hypothesis of every window (with its EOS when it ended on one). enc_row0 / r_enc: the windows' first
+        row and the batch the cross-K/V slot was encoded with (default 0 / W). align: also every window's token-level
+        timestamps, from the rows that fed its best hypothesis (_token_ts). enc_rows: each window's encoder row
+        (instead of enc_row0 + w: a fallback round's subset). criteria: also each best hypothesis' sum of
+        log-probabilities renormalised over the allowed tokens (the fallback's average log-probability numerator,
+        tw_beam_step's fin_lp) and, with no_speech_token, WhisperNoSpeechDetection's probability at the
+        <|startoftranscript|> step (PassResult.sum_logprob / no_speech_prob). options: DecodeOptions.make's
+        keywords (token_logprobs: the terms of that renormalised sum, tw_beam_step's fin_tlp)."""
+        opts = self._options(opts, options)
         nb, R = num_beams, W * num_beams
         r_enc = W if r_enc is None else r_enc
         if R > self.max_rows:
@@ -1571,99 +1562,67 @@ class WhisperEngine:
         dev = self.device
         T = self.d.max_target_positions
         bb = self._beam_buffers(R)
-        self._dec_context()
-        self.stream.wait_event(self._enc_ev[self._slot])
-        if enc_rows is not None:
-            self.dec_row_map[:R] = torch.as_tensor([int(enc_rows[w]) for w in range(W) for _ in range(nb)],
-                                                   dtype=torch.int32, device=dev)
-        else:
-            self.dec_row_map[:R] = enc_row0 + torch.arange(R, dtype=torch.int32, device=dev) // nb
-        self._use_dec_row_map = True
-        self._row_group = nb  # rows w * nb + j share window w's cross K/V
-        # self-attention K/V position table: every row starts on its own history; tw_beam_step points a continuing
-        # beam at its source's rows (no K/V copy: the reorder moved ~550 MB per step at 60 rows)
-        bb["kv_tab"][:R] = torch.arange(R, dtype=torch.int32, device=dev)[:, None]
-        self._kv_tab = bb["kv_tab"]
-        try:
-            # (a window's prefix on each of its beam rows)
-            base = self._prefill(R, None if prefix is None else
-                                 ([prefix[0][w] for w in range(W) for _ in range(nb)],
-                                  [prefix[1][w] for w in range(W) for _ in range(nb)]), r_enc)
-            # (a window's history prefix on each of its beam rows too)
-            self._hist_begin(R, repetition_penalty, no_repeat_ngram_size, tail,
-                             None if lang_ids is None else [int(x) for x in lang_ids for _ in range(nb)],
-                             None if prefix is None else ([prefix[0][w] for w in range(W) for _ in range(nb)], None),
-                             sequence_bias, bad_words_ids)
-            self.state[:R].zero_()
-            self.state[:R, _lib.TW_ST_LAST:_lib.TW_ST_LASTTS + 1] = -1
-            self.pos[:R] = base
-            self.ids[:R] = st.sot
-            detected = None
-            prompt_rest: List = []
-            if st.is_multilingual:
-                prompt_rest.append(None if lang_ids is None else [int(x) for x in lang_ids for _ in range(nb)])
-            prompt_rest.extend(int(t) for t in tail)
-            V = self.d.vocab
 
-            def no_speech() -> None:  # the logits of the step that fed <|startoftranscript|>
-                if no_speech_token is not None:
-                    _lib.call("tw_token_prob", self.logits.data_ptr(), R, V, V, int(no_speech_token),
-                              self.state.data_ptr(), self.stream.cuda_stream)
+        def per_row(xs):  # a window's value on each of its beam rows
+            return None if xs is None else [xs[w] for w in range(W) for _ in range(nb)]
 
-            for k, tok in enumerate(prompt_rest):
-                if k == 0 and st.is_multilingual and lang_ids is None:
-                    self.decoder_step(R, r_enc=r_enc)
-                    no_speech()
-                    self._select(R, self._select_params(1, max_new), tokens=False)  # ids <- lang, pos += 1
-                    detected = self.state[:R:nb, _lib.TW_ST_LANG].tolist()
-                    continue
-                self.decoder_step(R, with_logits=k == 0 and no_speech_token is not None, r_enc=r_enc)
-                if k == 0:
-                    no_speech()
-                if isinstance(tok, list):
-                    self.ids[:R] = torch.as_tensor(tok, dtype=torch.int32, device=dev)
-                else:
-                    self.ids[:R] = tok
-                self.pos[:R] = base + k + 1
+        lang_rows = per_row(lang_ids)
+        if prefix is not None:
+            prefix = (per_row(prefix[0]), per_row(prefix[1]))
+        tlp = opts.token_logprobs
+        # rows w * nb + j share window w's cross K/V. The self-attention K/V position table: every row starts on its
+        # own history; tw_beam_step points a continuing beam at its source's rows (no K/V copy: the reorder moved
+        # ~550 MB per step at 60 rows)
+        with self._pass(opts, align=(R, self._prompt_len(tail, prefix), max_new) if align else None,
+                        row_map=(torch.as_tensor(per_row(enc_rows), dtype=torch.int32, device=dev)
+                                 if enc_rows is not None else
+                                 enc_row0 + torch.arange(R, dtype=torch.int32, device=dev) // nb),
+                        row_group=nb, kv_tab=bb["kv_tab"]):
+            self._dec_context()
+            self.stream.wait_event(self._enc_ev[self._slot])
+            bb["kv_tab"][:R] = torch.arange(R, dtype=torch.int32, device=dev)[:, None]
+            base = self._prefill(R, prefix, r_enc)
+            self._hist_begin(R, tail, lang_rows, prefix and prefix[0])
+            ns_owed = self._prompt_phase(R, r_enc, base, lang_rows, tail, max_new, no_speech_token)
             bb["run_score"][:R].view(W, nb).fill_(-1e9)
             bb["run_score"][:R].view(W, nb)[:, 0] = 0.0
             bb["fin_score"][:R] = -1e9
             bb["fin_flag"][:R] = 0
             bb["fin_len"][:R] = 0
-            lps = criteria or token_logprobs  # (the per-token terms ride on the renormalised sums)
+            lps = criteria or tlp  # (the per-token terms ride on the renormalised sums)
             if lps:
                 bb["run_lp"][:R] = 0.0
                 bb["fin_lp"][:R] = 0.0
             bb["win"][:W] = torch.tensor([1, 0, 0, 0], dtype=torch.int32, device=dev)
             self.state[:R, _lib.TW_ST_NGEN] = 0
             sel = self._select_params(0, max_new, use_timestamps)
-            bp = _lib.TwBeamParams(nb, max_new, float(length_penalty), T, int(self._hist is not None))
+            bp = _lib.TwBeamParams(nb, max_new, opts.length_penalty, T, int(opts.history))
             bst = _lib.TwBeamState(bb["run_score"].data_ptr(), bb["fin_score"].data_ptr(), bb["fin_flag"].data_ptr(),
                                    bb["fin_len"].data_ptr(), bb["fin_tokens"].data_ptr(), bb["win"].data_ptr(),
                                    bb["src_rows"].data_ptr(), bb["kv_tab"].data_ptr(),
-                                   bb["fin_tab"].data_ptr() if self._align is not None else None,
+                                   bb["fin_tab"].data_ptr() if align else None,
                                    bb["run_lp"].data_ptr() if lps else None,
                                    bb["fin_lp"].data_ptr() if lps else None,
-                                   self.token_lp.data_ptr() if token_logprobs else None,  # (run_tlp: beside tokens)
-                                   bb["fin_tlp"].data_ptr() if token_logprobs else None)
-            s = self.stream.cuda_stream
+                                   self.token_lp.data_ptr() if tlp else None,  # (run_tlp: beside tokens)
+                                   bb["fin_tlp"].data_ptr() if tlp else None)
 
-            def step() -> None:
+            def step(after_decoder=None) -> None:
                 self.decoder_step(R, r_enc=r_enc)
+                if after_decoder is not None:
+                    after_decoder()
                 self._history(0, R, self.stream, to_logprobs=True)
                 _lib.call("tw_beam_step", self.logits.data_ptr(), W, self.d.vocab, self.suppress_bits.data_ptr(),
                           ctypes.byref(sel), ctypes.byref(bp), ctypes.byref(bst), self.state.data_ptr(),
-                          self.tokens.data_ptr(), self.ids.data_ptr(), self.pos.data_ptr(), bb["ws"].data_ptr(), s)
+                          self.tokens.data_ptr(), self.ids.data_ptr(), self.pos.data_ptr(), bb["ws"].data_ptr(),
+                          self._s)
 
-            # one beam step (decoder step over every row, tw_beam_step with its K/V table update) as one captured graph: the
-            # step reads its position, scores and histories from device memory, so the same graph serves every step
-            # (eager, each of its ~100 launches would be issued from the host every token)
+            # one beam step (decoder step over every row, tw_beam_step with its K/V table update) as one captured
+            # graph: the step reads its position, scores and histories from device memory, so the same graph serves
+            # every step (eager, each of its ~100 launches would be issued from the host every token)
             g = None
             if self.use_graphs:
-                al = self._align
-                key = ("beam", R, nb, max_new, bool(use_timestamps), float(length_penalty), self._slot, r_enc,
-                       self._masked, None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()),
-                       bool(criteria), self._dec_ctx, self._hist, bool(token_logprobs))
+                key = ("beam", R, nb, max_new, bool(use_timestamps), opts.length_penalty, self._slot, r_enc,
+                       self._masked, self._align_key(), bool(criteria), self._dec_ctx, opts.graph_key)
                 g = self._graphs.get(key)
                 if g is None:
                     g = torch.cuda.CUDAGraph()
@@ -1672,14 +1631,9 @@ class WhisperEngine:
                     self._graphs[key] = g
             steps = 0
             while steps < max_new:
-                if steps == 0 and not prompt_rest and no_speech_token is not None:
+                if steps == 0 and ns_owed:
                     # (a bare <|startoftranscript|> prompt: its step is the first beam step, eager with the probability)
-                    self.decoder_step(R, r_enc=r_enc)
-                    no_speech()
-                    self._history(0, R, self.stream, to_logprobs=True)
-                    _lib.call("tw_beam_step", self.logits.data_ptr(), W, V, self.suppress_bits.data_ptr(),
-                              ctypes.byref(sel), ctypes.byref(bp), ctypes.byref(bst), self.state.data_ptr(),
-                              self.tokens.data_ptr(), self.ids.data_ptr(), self.pos.data_ptr(), bb["ws"].data_ptr(), s)
+                    step(lambda: self._no_speech(R, no_speech_token))
                 elif g is not None:
                     g.replay()
                 else:
@@ -1690,17 +1644,19 @@ class WhisperEngine:
                         break
             flen = bb["fin_len"][:R:nb].tolist()
             ftok = bb["fin_tokens"][:R:nb].tolist()
-            sum_lp = bb["fin_lp"][:R:nb].tolist() if criteria else None
-            flp = bb["fin_tlp"][:R:nb].tolist() if token_logprobs else None
-            nsp = (self.state[:R:nb, _lib.TW_ST_NOSPEECH].contiguous().view(torch.float32).tolist()
-                   if no_speech_token is not None else None)
-        finally:
-            self._use_dec_row_map = False
-            self._row_group = 1
-            self._kv_tab = None
-        return PassResult([ftok[w][: flen[w]] for w in range(W)], detected if lang_ids is None else list(lang_ids),
-                          sum_logprob=sum_lp, no_speech_prob=nsp,
-                          token_lp=None if flp is None else [flp[w][: flen[w]] for w in range(W)])
+            # (the mode-1 selection alone writes TW_ST_LANG: tw_beam_step carries NGEN, LAST, PENULT, LASTTS, FINISHED)
+            res = PassResult([ftok[w][: flen[w]] for w in range(W)],
+                             self.state[:R:nb, _lib.TW_ST_LANG].tolist() if st.is_multilingual and lang_ids is None
+                             else None if lang_ids is None else list(lang_ids),
+                             sum_logprob=bb["fin_lp"][:R:nb].tolist() if criteria else None,
+                             no_speech_prob=(self.state[:R:nb, _lib.TW_ST_NOSPEECH].contiguous().view(torch.float32)
+                                             .tolist() if no_speech_token is not None else None))
+            if tlp:
+                flp = bb["fin_tlp"][:R:nb].tolist()
+                res.token_lp = [flp[w][: flen[w]] for w in range(W)]
+            if align:
+                self._token_ts(res, num_frames, nb)
+        return res
 
     def _chains(self, R: int) -> List[DecView]:
         """Contiguous row ranges of [0, R), one per decode chain (each with its own partial-sum buffer)."""
@@ -1721,10 +1677,8 @@ class WhisperEngine:
     def _graph_for(self, R: int, params, i: int, v: DecView, fused: bool = False,
                    n_steps: int = 1) -> Optional[torch.cuda.CUDAGraph]:
         """The captured decode step of chain i (n_steps > 1: that many steps back to back in one graph)."""
-        al = self._align
-        key = (R, params.max_new, params.use_timestamps, self._slot, i, fused,
-               None if al is None else (al["pos0"], al["n_steps"], al["buf"].data_ptr()), self._masked, self._dec_ctx,
-               n_steps, self._hist, self._tlp)
+        key = (R, params.max_new, params.use_timestamps, self._slot, i, fused, self._align_key(), self._masked,
+               self._dec_ctx, n_steps, self._opts.graph_key)
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -1774,9 +1728,7 @@ class WhisperEngine:
                  num_frames: Optional[Sequence[int]] = None, fallback: Optional[FallbackConfig] = None,
                  window_offset: int = 0, condition_on_prev_tokens: bool = False,
                  prompt_ids: Optional[Sequence[int]] = None,
-                 prompt_condition_type: Optional[str] = None, repetition_penalty: float = 1.0,
-                 no_repeat_ngram_size: int = 0, length_penalty: float = 1.0,
-                 token_logprobs: bool = False, sequence_bias=None, bad_words_ids=None) -> List[List[int]]:
+                 prompt_condition_type: Optional[str] = None, **options) -> List[List[int]]:
         """Whisper short-form generate() over feats[slot][:n_chunks] (each 3000 frames): language
         detection, the seek loop and segment extraction, returning for every chunk the concatenated
         segment tokens (what generate() returns before padding).
@@ -1794,16 +1746,10 @@ class WhisperEngine:
         (:1119-1124: behind <|startofprev|>, cut with the rest to the last 223 tokens) and "all-segments" puts it in
         front of the previous segments of every pass after the first (:1887-1888). The language is detected from the
         SOT step alone, before any prompt (detect_language); the prompt is not part of the returned tokens.
-        repetition_penalty / no_repeat_ngram_size: generate()'s history processors on every pass (each seek pass
-        starts a new history: its prompt + what it generated); length_penalty: beam search's exponent.
-        sequence_bias (a dict {tuple of ids: float} or a list of [ids, float]) / bad_words_ids (a list of id lists):
-        generate()'s SequenceBiasLogitsProcessor in front of those two and NoBadWordsLogitsProcessor behind them, on
-        the same history, in the same launch (tw_logits_history_bias); checked as transformers checks them, before
-        any work is queued.
-        token_logprobs: every pass also records each generated token's log-probability under the step's processed
-        scores (output_scores: after the history and Whisper processors and the warpers, at temperature 1 — the terms
-        of _retrieve_avg_logprobs): last_pass_logprobs parallel to last_passes, last_token_logprobs parallel to the
-        returned segment tokens (else both None). Tokens are those of the same call without it."""
+        options: DecodeOptions.make's keywords, checked before any work is queued and applied to every pass (each seek
+        pass starts a new history: its prompt + what it generated). With token_logprobs, last_pass_logprobs is
+        parallel to last_passes and last_token_logprobs to the returned segment tokens (else both None); the tokens are
+        those of the same call without it."""
         if slot is not None:
             self.use_slot(slot)
         if pre_encoded and n_chunks > self.max_batch:
@@ -1851,37 +1797,22 @@ class WhisperEngine:
             maxf = [self._long["T"]]
         else:
             maxf = [N_FRAMES] * n_chunks
-        passes = 0
         self.last_pass_prefixes: List[list] = [[] for _ in range(n_chunks)]
-        bias = {}
-        if sequence_bias is not None or bad_words_ids is not None:
-            seqbias.check_limits(  # (the checks raise here, ahead of the first pass)
-                seqbias.sequence_bias_entries(sequence_bias, self.d.vocab) if sequence_bias is not None else [],
-                seqbias.bad_words_entries(bad_words_ids, st.eot, self.d.vocab) if bad_words_ids is not None else [])
-            bias = {"sequence_bias": sequence_bias, "bad_words_ids": bad_words_ids}
-        try:
-            return self._seek_loop(n_chunks, tail, prompt_len, max_new_tokens, max_new, seek, segs, passes_raw, langs,
-                                   tts, maxf, seg_lists, do_cond, prev_sot, condition_on_prev_tokens, max_passes,
-                                   pre_encoded, num_beams, word_timestamps, num_frames, fb, return_timestamps,
-                                   window_offset, prompt,
-                                   hist={"repetition_penalty": float(repetition_penalty or 1.0),
-                                         "no_repeat_ngram_size": int(no_repeat_ngram_size or 0), **bias},
-                                   length_penalty=float(1.0 if length_penalty is None else length_penalty),
-                                   token_logprobs=bool(token_logprobs))
-        finally:
-            self._masked = False
+        opts = self._options(None, options)  # (the checks raise here, ahead of the first pass)
+        return self._seek_loop(n_chunks, tail, prompt_len, max_new_tokens, max_new, seek, segs, passes_raw, langs, tts,
+                               maxf, seg_lists, do_cond, prev_sot, condition_on_prev_tokens, max_passes, pre_encoded,
+                               num_beams, word_timestamps, num_frames, fb, return_timestamps, window_offset, prompt,
+                               opts)
 
     def _seek_loop(self, n_chunks, tail, prompt_len, max_new_tokens, max_new, seek, segs, passes_raw, langs, tts, maxf,
                    seg_lists, do_cond, prev_sot, condition, max_passes, pre_encoded, num_beams, word_timestamps,
-                   num_frames, fb, return_timestamps, window_offset, prompt=None, hist=None, length_penalty=1.0,
-                   token_logprobs=False):
+                   num_frames, fb, return_timestamps, window_offset, prompt, opts: DecodeOptions):
         st = self.gen.special
-        hist = hist or {}
+        token_logprobs = opts.token_logprobs
         passes = 0
         # token_logprobs: per chunk the kept tokens' log-probabilities (beside segs) and every pass's (beside passes_raw)
         tlps: List[List[float]] = [[] for _ in range(n_chunks)]
         passes_lp: List[List[List[float]]] = [[] for _ in range(n_chunks)]
-        lpkw = {"token_logprobs": True} if token_logprobs else {}
         while any(seek[i] < maxf[i] for i in range(n_chunks)):
             rows = [i for i in range(n_chunks) if seek[i] < maxf[i]]
             per = self.max_batch if num_beams == 1 else min(self.max_batch, self.max_rows // num_beams)
@@ -1929,8 +1860,7 @@ class WhisperEngine:
                     toks_f, skip_f, lang_f, temp_f, nb_left, ts_f, lp_f = self._fallback_pass(
                         R, tail, given, mnew, return_timestamps, fb, [window_offset + i for i in part], passes,
                         enc_row0=b0 if pre else 0, r_enc=n_chunks if pre else R, prefix=pfx, num_beams=num_beams,
-                        align=word_timestamps, num_frames=nf_part, hist=hist, length_penalty=length_penalty,
-                        token_logprobs=token_logprobs)
+                        align=word_timestamps, num_frames=nf_part, opts=opts)
                     num_beams = nb_left  # (a sampling round left generation_config.num_beams = 1)
                     for j in range(R):  # (by position in the pass's batch, as transformers writes it)
                         do_cond[j] = bool(condition) and (temp_f[j] is None or temp_f[j] < 0.5)
@@ -1957,12 +1887,10 @@ class WhisperEngine:
                     pre = pre_encoded and passes == 0
                     res = self.beam_pass(R, num_beams, tail, given, mnew, use_timestamps=return_timestamps,
                                          enc_row0=b0 if pre else 0, r_enc=n_chunks if pre else R, prefix=pfx,
-                                         align=word_timestamps, num_frames=nf_part, length_penalty=length_penalty,
-                                         **hist, **lpkw)
+                                         align=word_timestamps, num_frames=nf_part, opts=opts)
                 else:
                     res = self.decode_pass(R, tail, given, mnew, use_timestamps=return_timestamps,
-                                           align=word_timestamps, num_frames=nf_part, prefix=pfx, **hist, **lpkw)
-                self._masked = False
+                                           align=word_timestamps, num_frames=nf_part, prefix=pfx, opts=opts)
                 for j in range(R):
                     do_cond[j] = bool(condition)
                 for j, i in enumerate(part):
@@ -2002,8 +1930,7 @@ class WhisperEngine:
     def _fallback_pass(self, R: int, tail, given, max_new: int, return_timestamps: bool, fb: FallbackConfig,
                        windows: Sequence[int], pass_no: int, enc_row0: int = 0, r_enc: Optional[int] = None,
                        prefix=None, num_beams: int = 1, align: bool = False,
-                       num_frames: Optional[Sequence[int]] = None, hist: Optional[dict] = None,
-                       length_penalty: float = 1.0, token_logprobs: bool = False):
+                       num_frames: Optional[Sequence[int]] = None, opts: DecodeOptions = NO_OPTIONS):
         """generate_with_fallback (generation_whisper.py:970-1116) for one seek pass of R encoded rows: decode at
         the first temperature, re-decode the rows whose criteria fail at the next one, until none does or the
         temperatures run out. Returns per row the kept sequence (EOS removed), should_skip, the language ids, each
@@ -2030,7 +1957,7 @@ class WhisperEngine:
         ns_pass: Optional[List[float]] = None  # the first round's no-speech probabilities (the whole pass's rows)
         row_ts: List[Optional[np.ndarray]] = [None] * R
         row_lp: List[Optional[List[float]]] = [None] * R
-        lpkw = {"token_logprobs": True} if token_logprobs else {}
+        token_logprobs = opts.token_logprobs
         for fi, t in enumerate(temps):
             do_sample = t is not None and t > 0.0
             if do_sample:
@@ -2041,16 +1968,14 @@ class WhisperEngine:
             if nb > 1:
                 res = self.beam_pass(len(idx), nb, tail, sub_lang, max_new, use_timestamps=return_timestamps,
                                      enc_rows=[enc_row0 + i for i in idx], r_enc=r_enc, prefix=sub_pfx,
-                                     criteria=True, no_speech_token=ns_tok, align=align, num_frames=sub_nf,
-                                     length_penalty=length_penalty, **(hist or {}), **lpkw)
+                                     criteria=True, no_speech_token=ns_tok, align=align, num_frames=sub_nf, opts=opts)
             else:
                 res = self.sample_pass(len(idx), tail, sub_lang, max_new,
                                        temperature=float(t) if do_sample else 0.0, top_k=fb.top_k, seed=fb.seed,
                                        row_keys=[fallback_row_key(windows[i], pass_no, fi) for i in idx],
                                        use_timestamps=return_timestamps, enc_rows=[enc_row0 + i for i in idx],
                                        r_enc=r_enc, no_speech_token=ns_tok, prefix=sub_pfx, align=align,
-                                       num_frames=sub_nf, **(hist or {}), **lpkw)
-            self._masked = False
+                                       num_frames=sub_nf, opts=opts)
             if align:
                 for j, i in enumerate(idx):
                     row_ts[i] = res.token_ts[j]
