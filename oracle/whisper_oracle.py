@@ -452,8 +452,28 @@ def _topk_desc(x: np.ndarray, k: int) -> np.ndarray:
     return cand[np.lexsort((cand, -x[cand]))][:k]
 
 
+def _beam_step_record(logits, run_tok, run_score, fin_score, acc, g: GenCfg, use_ts: bool, K: int) -> dict:
+    """The per-beam part of beam_search_core's on_step record, from the values a step starts with: lse (the rows'
+    log_softmax denominators), margin / fires (the timestamp rule's _ts_rule_margin on the processed scores and its
+    decision), the step's input beams, and the K + 1 best accumulated scores with their flat indices (the K + 1-th
+    is the one the top-K left out)."""
+    nb = len(logits)
+    lse = np.empty(nb, np.float32)
+    margin = np.full(nb, -np.inf)
+    for b in range(nb):
+        x = np.asarray(logits[b], np.float32)
+        m = np.max(x)
+        lse[b] = m + np.log(np.sum(np.exp(x - m), dtype=np.float32))
+        if use_ts:
+            margin[b] = _ts_rule_margin(process_logits_no_rule(_log_softmax32(x), run_tok[b], g), g.ts_begin)
+    near = _topk_desc(acc, K + 1)
+    return {"lse": lse, "margin": margin, "fires": margin > 0, "prev_run_tok": [list(t) for t in run_tok],
+            "prev_run_score": run_score.copy(), "prev_fin_score": fin_score.copy(), "near_idx": near,
+            "near_val": acc[near].astype(np.float32)}
+
+
 def beam_search_core(first_logits: np.ndarray, step_fn, P: int, max_new: int, g: GenCfg, use_ts: bool,
-                     num_beams: int, length_penalty: float = 1.0) -> Tuple[List[int], dict]:
+                     num_beams: int, length_penalty: float = 1.0, on_step=None) -> Tuple[List[int], dict]:
     """GenerationMixin._beam_search ($TF/generation/utils.py:3208-3512) for ONE window with the Whisper processor
     chain, early_stopping=False (GenerationConfig default), one EOS id: K = 2 * num_beams continuations per step
     (:3277-3282) from log_softmax(f32 logits) + processors (:3381-3382) + the running beam scores; running beams =
@@ -462,7 +482,9 @@ def beam_search_core(first_logits: np.ndarray, step_fn, P: int, max_new: int, g:
     one (:3008-3053) or every candidate hit a stopping criterion (EOS / max_length, :3055-3073).
     first_logits: f32[V] after the prompt; step_fn(src_beams, tokens) -> f32[nb][V]: reorder the beams' decoder
     caches to src_beams, feed tokens, return the next logits. Returns (generated tokens of the best finished beam,
-    with its EOS if it ended on one; a trace dict of the final finished/running beams)."""
+    with its EOS if it ended on one; a trace dict of the final finished/running beams).
+    on_step(record): called once per iteration, after the running beams are reordered, with plain copies of that
+    step's values (see _beam_step_record); None changes nothing."""
     nb, K, V = num_beams, 2 * num_beams, g.V
     max_length = P + max_new
     logits = [first_logits] * nb
@@ -479,6 +501,8 @@ def beam_search_core(first_logits: np.ndarray, step_fn, P: int, max_new: int, g:
         for b in range(nb):
             lp = process_logits(_log_softmax32(logits[b]), run_tok[b], g, use_ts)
             acc[b * V:(b + 1) * V] = lp + run_score[b]
+        if on_step is not None:
+            rec = _beam_step_record(logits, run_tok, run_score, fin_score, acc, g, use_ts, K)
         top = _topk_desc(acc, K)
         sc = acc[top].astype(np.float32)
         src, tok = top // V, top % V
@@ -512,6 +536,14 @@ def beam_search_core(first_logits: np.ndarray, step_fn, P: int, max_new: int, g:
         best_possible = run_score[0] / np.float32((cur_len - P) ** length_penalty)
         worst = np.where(fin_flag, np.min(fin_score), np.float32(-1e9))
         unsatisfied = unsatisfied and bool(np.any(best_possible > worst))
+        if on_step is not None:
+            rec.update(src=src.copy(), tok=tok.copy(), sc=sc.copy(), hits=hits.copy(), rsc=rsc.copy(),
+                       order=np.array(order), srcs=np.array(srcs), merged=merged.copy(), msel=np.array(msel),
+                       run_tok=[list(t) for t in run_tok], run_score=run_score.copy(), fin_score=fin_score.copy(),
+                       fin_seq=[list(t) for t in fin_seq], fin_flag=fin_flag.copy(), unsatisfied=unsatisfied,
+                       all_hits=bool(np.all(hits)), best_possible=np.float32(best_possible), worst=np.array(worst),
+                       steps=cur_len - P)
+            on_step(rec)
         if not unsatisfied or bool(np.all(hits)):
             break
         logits = step_fn(srcs, [t[-1] for t in run_tok])
