@@ -378,6 +378,16 @@ int tw_attn_decode_cross_probs(const uint16_t* q, int B, int H, int S, int Bt, c
  * _dynamic_time_warping (generation_whisper.py:64-114); text_idx / time_idx int32[n + m] receive the path,
  * *path_len its length. */
 int tw_dtw(const double* matrix, int n, int m, int* text_idx, int* time_idx, int* path_len);
+/* The DTW cost matrix from tw_attn_decode_cross_probs' recording buffer, per row over that row's own extent
+ * (csrc/align.hip): probs f32[B][n_steps][n_slots][S] -> cost f32[B][n_steps][S]. With z = (p - mean_k p) / std_k p,
+ * mean and population standard deviation over the row's first n_rows[b] steps per (slot, frame) in f32,
+ *   cost[b][k][f] = -(1 / n_slots) * sum_slot median_width(z[slot][k][0:n_frames[b]])[f]
+ * for k < n_rows[b], f < n_frames[b]: reflect padding of width / 2, the middle of the sorted window, NaN last
+ * (_median_filter, generation_whisper.py:43-61); a row of n_frames[b] <= width / 2 frames is not filtered. Nothing
+ * else of cost is written, and rows with n_rows[b] < 2 or n_frames[b] < 1 are left untouched (n_rows / n_frames are
+ * device int32[B], clamped to n_steps / S). width: odd, 1..15; anything else is an error. */
+int tw_align_cost(const float* probs, int B, int n_steps, int n_slots, int S, const int* n_rows, const int* n_frames,
+                  int width, float* cost, void* stream);
 
 /* ---- fp32 path (BASELINE configs[0]: whisper-tiny.en fp32) --------------------------------------------------
  * The same modules as the bf16 entries above at f32 operand / activation / cache precision, for the reference's
@@ -468,6 +478,18 @@ int tw_token_logprob(const float* logits, int B, int ld_logits, const uint32_t* 
 /* state[b][TW_ST_NOSPEECH] (f32 bits) = softmax(logits[b][0:V])[token]: WhisperNoSpeechDetection's no_speech_prob
  * ($TF/generation/logits_process.py:2050-2112) from the logits at the <|startoftranscript|> position. */
 int tw_token_prob(const float* logits, int B, int ld_logits, int V, int token, int* state, void* stream);
+/* Teacher-forced selection (forced alignment), in tw_logits_select's place in a decode step; one workgroup per row.
+ * With n = state[b][TW_ST_NGEN]: while n < force_len[b] the row commits tok = force[b][n] (force int32[B][ld_force]):
+ * lp_out[b][n] = logits[b][tok] - logsumexp(logits[b][0:V]) (f32, the raw logits: no processor runs, nothing is
+ * chosen), tokens_out[b][n] = next_ids[b] = tok, TW_ST_NGEN += 1 and TW_ST_LAST / TW_ST_PENULT move as in the
+ * selection kernels. Otherwise TW_ST_FINISHED = 1, next_ids[b] = pad, and tokens_out[b][n] = pad, lp_out[b][n] = 0.0
+ * when n < ld_tokens. pos[b] += 1 in both cases (pos NULL: none), so a captured step replays unchanged. Columns
+ * [V, ld_logits) are never read. Every other pointer is required. A forced id outside [0, V) is a contract
+ * violation: the TW_DEBUG build fails the call (outside a graph capture), the product build reads no logit for it
+ * and writes NaN. */
+int tw_logits_force(const float* logits, int B, int ld_logits, int V, const int* force, int ld_force,
+                    const int* force_len, int pad, int* state, int* tokens_out, int ld_tokens, int* next_ids, int* pos,
+                    float* lp_out, int ld_lp, void* stream);
 
 /* RepetitionPenaltyLogitsProcessor then NoRepeatNGramLogitsProcessor ($TF/generation/logits_process.py), in place on
  * rows [0, R) of f32 logits, ahead of tw_logits_select / _select_embed / _sample / tw_beam_step (generate() puts both

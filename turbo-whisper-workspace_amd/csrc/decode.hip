@@ -620,6 +620,118 @@ extern "C" int tw_token_prob(const float* logits, int B, int ld_logits, int V, i
 }
 
 // =================================================================================================
+// Teacher-forced selection (forced alignment): the step's token is given, not chosen. grid B, 256 threads per row,
+// in tw_logits_select's place in a decode step. n = state[b][TW_ST_NGEN]; while n < force_len[b] the row commits
+// force[b][n] with its log-probability under the RAW logits (f32 log_softmax over [0, V): no processors, nothing is
+// being chosen), afterwards it is finished and feeds pad. pos advances either way, so a captured step replays
+// unchanged for as many steps as the longest row needs, with no finished check on the host.
+// Every index the kernel forms is bounded by its own ld (a forced id outside [0, V) reads no logit: its lp is NaN;
+// the TW_DEBUG build reports it instead).
+// =================================================================================================
+__global__ TW_DEC_LB(256, 1) void k_logits_force(const float* __restrict__ logits, int ld_logits, int V,
+                                                 const int* __restrict__ force, int ld_force,
+                                                 const int* __restrict__ force_len, int pad, int* __restrict__ state,
+                                                 int* __restrict__ tokens_out, int ld_tokens,
+                                                 int* __restrict__ next_ids, int* __restrict__ pos,
+                                                 float* __restrict__ lp_out, int ld_lp) {
+  TW_DEC_PRIO();
+  __shared__ float red[8];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int* st = state + b * TW_STATE_STRIDE;
+  const int n = st[TW_ST_NGEN];  // (thread 0 rewrites it behind block_lse256's barriers)
+  const int flen = min(force_len[b], ld_force);
+  if (n < 0 || n >= flen) {  // (uniform per block) past the row's end
+    if (tid == 0) {
+      if (pos) pos[b] += 1;
+      st[TW_ST_FINISHED] = 1;
+      next_ids[b] = pad;
+      if (n >= 0 && n < ld_tokens) tokens_out[(size_t)b * ld_tokens + n] = pad;
+      if (n >= 0 && n < ld_lp) lp_out[(size_t)b * ld_lp + n] = 0.f;
+    }
+    return;
+  }
+  const int tok = force[(size_t)b * ld_force + n];
+  const float* row = logits + (size_t)b * ld_logits;
+  float m = -INFINITY, s = 0.f;
+  for (int v = tid; v < V; v += 256) lse_merge(m, s, row[v], 1.f);
+  block_lse256(m, s, red);
+  if (tid != 0) return;
+  if (pos) pos[b] += 1;
+  const float lp = (tok >= 0 && tok < V) ? row[tok] - (m + logf(s)) : __int_as_float(0x7fc00000);
+  if (n < ld_lp) lp_out[(size_t)b * ld_lp + n] = lp;
+  if (n < ld_tokens) tokens_out[(size_t)b * ld_tokens + n] = tok;
+  next_ids[b] = tok;
+  st[TW_ST_PENULT] = st[TW_ST_LAST];
+  st[TW_ST_LAST] = tok;
+  st[TW_ST_NGEN] = n + 1;
+}
+
+#if TW_DEBUG
+// Debug builds: outside a graph capture, every forced id the launch is about to commit is checked against [0, V)
+// first (the check synchronises the stream) and the call fails with TW_ERR_ARG instead of yielding a NaN.
+__global__ __launch_bounds__(64) void k_force_check(const int* __restrict__ force, int ld_force,
+                                                    const int* __restrict__ force_len, const int* __restrict__ state,
+                                                    int V, int B, int* __restrict__ bad) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const int n = state[b * TW_STATE_STRIDE + TW_ST_NGEN];
+  int r = 0;
+  if (n >= 0 && n < min(force_len[b], ld_force)) {
+    const int tok = force[(size_t)b * ld_force + n];
+    r = (tok < 0 || tok >= V) ? 1 : 0;
+  }
+  bad[b] = r;
+}
+static int tw_debug_force_guard(const int* force, int ld_force, const int* force_len, const int* state, int V, int B,
+                                hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return TW_OK;
+  static int* d_bad = nullptr;
+  static int cap = 0;
+  if (cap < B) {
+    if (d_bad) (void)hipFree(d_bad);
+    cap = 0;
+    if (hipMalloc(&d_bad, sizeof(int) * B) != hipSuccess) {
+      d_bad = nullptr;
+      tw_set_error("tw_logits_force (debug): hipMalloc failed");
+      return TW_ERR_LAUNCH;
+    }
+    cap = B;
+  }
+  hipLaunchKernelGGL(k_force_check, dim3(tw_cdiv(B, 64)), dim3(64), 0, st, force, ld_force, force_len, state, V, B,
+                     d_bad);
+  int* h = (int*)alloca(sizeof(int) * B);
+  if (hipMemcpyAsync(h, d_bad, sizeof(int) * B, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    tw_set_error("tw_logits_force (debug): the forced-id check failed to run");
+    return TW_ERR_LAUNCH;
+  }
+  for (int b = 0; b < B; ++b)
+    if (h[b]) {
+      tw_set_error("tw_logits_force: precondition violated: row %d's next forced id is outside [0, %d)", b, V);
+      return TW_ERR_ARG;
+    }
+  return TW_OK;
+}
+#endif
+
+extern "C" int tw_logits_force(const float* logits, int B, int ld_logits, int V, const int* force, int ld_force,
+                               const int* force_len, int pad, int* state, int* tokens_out, int ld_tokens,
+                               int* next_ids, int* pos, float* lp_out, int ld_lp, void* stream) {
+  TW_REQUIRE(logits && force && force_len && state && tokens_out && next_ids && lp_out,
+             "tw_logits_force: null pointer");
+  TW_REQUIRE(B > 0 && ld_force > 0 && ld_tokens > 0 && ld_lp > 0, "tw_logits_force: B=%d ld_force=%d ld_tokens=%d "
+             "ld_lp=%d", B, ld_force, ld_tokens, ld_lp);
+  TW_REQUIRE(V > 0 && V <= ld_logits, "tw_logits_force: V=%d ld=%d", V, ld_logits);
+#if TW_DEBUG
+  if (int rc = tw_debug_force_guard(force, ld_force, force_len, state, V, B, (hipStream_t)stream)) return rc;
+#endif
+  hipLaunchKernelGGL(k_logits_force, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ld_logits, V, force, ld_force,
+                     force_len, pad, state, tokens_out, ld_tokens, next_ids, pos, lp_out, ld_lp);
+  return tw_check_launch("tw_logits_force");
+}
+
+// =================================================================================================
 // History processors in front of the Whisper chain: RepetitionPenaltyLogitsProcessor
 // ($TF/generation/logits_process.py: gather, where(score < 0, score * p, score / p), scatter) then
 // NoRepeatNGramLogitsProcessor (_calc_banned_ngram_tokens: every token that followed an earlier occurrence of the

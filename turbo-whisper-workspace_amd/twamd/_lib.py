@@ -57,7 +57,7 @@ EXPORTED = (
     "tw_aac_adts_probe", "tw_aac_adts_decode", "tw_dec_fused", "tw_dec_fused_sync_bytes", "tw_dec_fused_supported",
     "tw_dec_fused_set_grid", "tw_dec_fused_set_acquire", "tw_dec_fused_set_probe", "tw_dec_fused_grid",
     "tw_dec_fused_xpart_bytes", "tw_logits_history", "tw_token_logprob", "tw_logits_sample_lp",
-    "tw_logits_history_bias",
+    "tw_logits_history_bias", "tw_logits_force", "tw_align_cost",
 )
 
 
@@ -177,6 +177,8 @@ _SIGS = {
                              _P, _P, _I, _P, _P, _P, _I, _P], _I),
     "tw_token_logprob": ([_P, _I, _I, _P, ctypes.POINTER(TwSelectParams), _P, _P, _I, _P], _I),
     "tw_token_prob": ([_P, _I, _I, _I, _I, _P, _P], _I),
+    "tw_logits_force": ([_P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _I, _P], _I),
+    "tw_align_cost": ([_P, _I, _I, _I, _I, _P, _P, _I, _P, _P], _I),
     "tw_logits_history": ([_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _F, _I, _I, _P], _I),
     "tw_logits_history_bias": ([_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _F, _I, _I, ctypes.POINTER(TwSeqBias), _P],
                                _I),

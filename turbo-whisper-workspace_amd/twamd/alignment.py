@@ -38,6 +38,15 @@ def dtw(cost: np.ndarray):
     return ti[: ln.value], tj[: ln.value]
 
 
+def times_from_cost(cost: np.ndarray, time_precision: float = 0.02) -> np.ndarray:
+    """A finished cost matrix f32 [rows][frames] (tw_align_cost: minus the smoothed, head-averaged attention) ->
+    f32 [rows + 1] seconds: the DTW path's text-index jumps, as token_timestamps derives them from its own matrix."""
+    ti, tj = dtw(np.asarray(cost, np.float64))
+    jumps = np.concatenate([[True], np.diff(ti) != 0])
+    jt = tj[jumps] * time_precision
+    return np.concatenate([jt, [jt[-1]]]).astype(np.float32)
+
+
 def token_timestamps(weights: np.ndarray, num_input_ids: int, num_frames: Optional[int], median_width: int = 7,
                      time_precision: float = 0.02) -> np.ndarray:
     """weights f32 [heads][rows][frames] of the fed positions (prompt rows first) -> f32 [rows + 1] seconds."""

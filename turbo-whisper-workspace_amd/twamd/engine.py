@@ -378,6 +378,12 @@ class WhisperEngine:
         self._bias_len = torch.zeros(_lib.TW_SEQBIAS_MAX_ENTRIES, dtype=i32, device=dev)
         self._bias_val = torch.zeros(_lib.TW_SEQBIAS_MAX_ENTRIES, dtype=torch.float32, device=dev)
         self._bias_key: Optional[tuple] = None
+        # force_pass (forced alignment): per row the tokens tw_logits_force commits and their count, and the rows'
+        # extents tw_align_cost standardises over; fixed addresses (captured steps hold them), contents per pass
+        self._force_ids = torch.zeros(self.max_rows, T, dtype=i32, device=dev)
+        self._force_len = torch.zeros(self.max_rows, dtype=i32, device=dev)
+        self._force_ext = torch.zeros(2, self.max_rows, dtype=i32, device=dev)  # [n_rows | n_frames]
+        self._force_cost: Optional[torch.Tensor] = None  # tw_align_cost's output, grown on demand
         # the library's (tw_gemv_set_wide_slices, tw_gemv_set_variant) state (its defaults) and whether the decoder's
         # layers run as one persistent launch (tw_dec_fused) in the current pass
         self._dec_ctx = (1, 0, False)
@@ -1363,6 +1369,137 @@ class WhisperEngine:
             if align:
                 self._token_ts(res, num_frames)
         return res
+
+    def _force(self, R: int) -> None:
+        """tw_logits_force on the logits of rows [0, R): the pass's next given token in tw_logits_select's place."""
+        _lib.call("tw_logits_force", self.logits.data_ptr(), R, self.logits.stride(0), self.d.vocab,
+                  self._force_ids.data_ptr(), self._force_ids.stride(0), self._force_len.data_ptr(),
+                  self.gen.special.eot, self.state.data_ptr(), self.tokens.data_ptr(), self.tokens.stride(0),
+                  self.ids.data_ptr(), self.pos.data_ptr(), self.token_lp.data_ptr(), self.token_lp.stride(0), self._s)
+
+    @on_engine_streams
+    def force_pass(self, R: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]],
+                   forced: Sequence[Sequence[int]], num_frames: Optional[Sequence[int]] = None) -> PassResult:
+        """Forced alignment of R encoded rows with given text: forced[r] (text token ids) followed by
+        <|endoftext|> is fed through the decoder from the prompt [SOT, (lang), *tail] (the language detected when
+        lang_ids is None on a multilingual model, as decode_pass), teacher-forced on the device: every step after
+        the prompt is decoder_step + tw_logits_force, captured once and replayed, with no finished check and no host
+        synchronisation until the last step is queued. Returns tokens (the forced ids + EOT), token_lp (the model's
+        own log-probability of each, raw logits: nothing is chosen, so no processor runs) and token_ts in _token_ts's
+        layout (prompt zeros, one time per token).
+
+        Unlike _token_ts, which standardises a batch over its padded length, every row's times come from that row's
+        own fed tokens (len(forced[r])) and its own frame crop (num_frames[r] // 2, at most 1500): a chunk's alignment
+        does not depend on its neighbours in the batch. tw_align_cost builds the cost matrices on the device; one copy
+        brings the cropped blocks to the host, where DTW (tw_dtw) and the jump times are token_timestamps'."""
+        st = self.gen.special
+        if len(forced) != R or not 0 < R <= self.max_batch:
+            raise ValueError(f"force_pass: {len(forced)} token lists for {R} rows (max_batch {self.max_batch})")
+        P = self._prompt_len(tail)
+        rows = [[int(t) for t in f] + [st.eot] for f in forced]
+        lens = [len(r) for r in rows]
+        max_len, limit = max(lens), self.max_new_for(P)
+        for r, row in enumerate(rows):
+            if len(row) > limit:
+                raise ValueError(f"force_pass: row {r} has {len(row)} tokens with <|endoftext|>, more than the "
+                                 f"{limit} a prompt of {P} leaves")
+            if any(not 0 <= t < self.d.vocab for t in row):
+                raise ValueError(f"force_pass: row {r} holds an id outside the vocabulary [0, {self.d.vocab})")
+        if num_frames is not None and len(num_frames) != R:
+            raise ValueError("force_pass: one num_frames per row")
+        detect = st.is_multilingual and lang_ids is None
+        with self._pass(NO_OPTIONS, align=(R, P, max_len)):
+            self._dec_context()
+            self.stream.wait_event(self._enc_ev[self._slot])  # the cross-K/V of this slot is written
+            table = np.full((R, max_len), st.eot, np.int32)
+            for r, row in enumerate(rows):
+                table[r, : len(row)] = row
+            self._force_ids[:R, :max_len] = torch.from_numpy(table).to(self.device)
+            self._force_len[:R] = torch.tensor(lens, dtype=torch.int32, device=self.device)
+
+            def prompt() -> None:  # the prompt steps and the first given token (scored from the last prompt token)
+                self._prompt_phase(R, R, 0, lang_ids, tail, max_len)
+                self.decoder_step(R)
+                self._force(R)
+
+            def step() -> None:  # feeds the token the previous step committed, commits (and scores) the next
+                self.decoder_step(R)
+                self._force(R)
+
+            # both graphs are captured before anything is replayed (a capture synchronises the device): from the
+            # prompt to the last step the host only queues
+            gp = gs = None
+            if self.use_graphs:
+                key = ("force", R, self._slot, self._align_key(), self._dec_ctx)
+                if self.prompt_graph and (detect or not st.is_multilingual):
+                    gp = self._captured(key + ("prompt", tuple(int(t) for t in tail)), prompt)
+                if max_len > 1:
+                    gs = self._captured(key + ("step",), step)
+            gp.replay() if gp is not None else prompt()
+            ev0 = None
+            if self.pass_events is not None:  # (measurement: HIP events around the steps, as _chain_loop's)
+                ev0 = torch.cuda.Event(enable_timing=True)
+                ev0.record(self.stream)
+                th0 = time.perf_counter()
+            for _ in range(max_len - 1):  # the last given token (<|endoftext|> of the longest row) is never fed
+                gs.replay() if gs is not None else step()
+            if ev0 is not None:
+                ev1 = torch.cuda.Event(enable_timing=True)
+                ev1.record(self.stream)
+                self.pass_events.append((ev0, ev1, max_len - 1, time.perf_counter() - th0))
+            ts = self._force_times(R, [n - 1 for n in lens], num_frames)
+            toks = self.tokens[:R, :max_len].tolist()
+            lps = self.token_lp[:R, :max_len].tolist()
+            res = PassResult([toks[r][: lens[r]] for r in range(R)],
+                             self.state[:R, _lib.TW_ST_LANG].tolist() if detect else
+                             None if lang_ids is None else list(lang_ids))
+            res.token_lp = [lps[r][: lens[r]] for r in range(R)]
+            res.token_ts = [np.concatenate([np.zeros(P, np.float32), t]) for t in ts]
+        return res
+
+    def _force_times(self, R: int, n_rows: Sequence[int], num_frames: Optional[Sequence[int]]) -> List[np.ndarray]:
+        """Per row the token times (f32 [n_rows[r] + 1], no prompt zeros) from the probabilities the pass in progress
+        recorded (self._align): each row over its own n_rows[r] fed tokens and its own crop num_frames[r] // 2 (at
+        most 1500). tw_align_cost builds the cost matrices on the device, one copy brings the cropped blocks to the
+        host, then tw_dtw and the jump times per row. A row with a single fed token (or no frame) goes through
+        alignment.token_timestamps on its probabilities, as _token_ts would take it."""
+        al = self._align
+        n_steps, n_slots = al["n_steps"], al["n_slots"]
+        n_fr = [S_ENC if num_frames is None else max(0, min(S_ENC, int(num_frames[r]) // 2)) for r in range(R)]
+        self._force_ext[:, :R] = torch.tensor([list(n_rows), n_fr], dtype=torch.int32, device=self.device)
+        need = R * n_steps * S_ENC
+        if self._force_cost is None or self._force_cost.numel() < need:
+            self._force_cost = torch.empty(need, dtype=torch.float32, device=self.device)
+        cost = self._force_cost[:need].view(R, n_steps, S_ENC)
+        _lib.call("tw_align_cost", al["buf"].data_ptr(), R, n_steps, n_slots, S_ENC, self._force_ext[0].data_ptr(),
+                  self._force_ext[1].data_ptr(), self.gen.median_filter_width, cost.data_ptr(), self._s)
+        on_gpu = [r for r in range(R) if n_rows[r] >= 2 and n_fr[r] >= 1]
+        blocks = (torch.cat([cost[r, : n_rows[r], : n_fr[r]].reshape(-1) for r in on_gpu]).cpu().numpy()
+                  if on_gpu else np.zeros(0, np.float32))
+        probs = al["buf"][: R * n_steps * n_slots * S_ENC].view(R, n_steps, n_slots, S_ENC)
+        out, off = [], 0
+        for r in range(R):
+            if r in on_gpu:
+                n = n_rows[r] * n_fr[r]
+                out.append(alignment.times_from_cost(blocks[off: off + n].reshape(n_rows[r], n_fr[r])))
+                off += n
+            elif n_rows[r] >= 1:
+                w = probs[r, : n_rows[r]].permute(1, 0, 2)[al["perm"]].float().cpu().numpy()
+                out.append(alignment.token_timestamps(w, 0, None if num_frames is None else int(num_frames[r]),
+                                                      self.gen.median_filter_width))
+            else:
+                out.append(np.zeros(1, np.float32))
+        return out
+
+    def _captured(self, key: tuple, fn) -> "torch.cuda.CUDAGraph":
+        """The graph of fn's launches on the engine stream under key, captured (not executed) on first use."""
+        g = self._graphs.get(key)
+        if g is None:
+            g = torch.cuda.CUDAGraph()
+            with _capture(g, self.stream):
+                fn()
+            self._graphs[key] = g
+        return g
 
     def _chain_loop(self, R: int, params, max_new: int, check_every: int) -> None:
         """decode_pass's generation steps after the first: the rows split into chains on their own high-priority

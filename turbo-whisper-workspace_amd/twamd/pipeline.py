@@ -25,7 +25,7 @@ from .engine import WhisperEngine
 from .engine_f32 import WhisperEngineF32
 from .frontend import CHUNK_SAMPLES, SAMPLE_RATE, Window, chunk_windows, time_precision
 from .segments import FallbackConfig, pad_right
-from .tokenizer import LANGUAGE_NAMES, WhisperVocab, decode_asr
+from .tokenizer import LANGUAGE_NAMES, WhisperVocab, collate_word_timestamps, decode_asr, mean_logprob
 from .weights import build_weights
 
 _NAME_TO_CODE = {v: k for k, v in LANGUAGE_NAMES.items()}
@@ -263,6 +263,90 @@ class TurboTranscriber:
         text, optional = (dist.stitch_sharded(self.vocab, model_outputs, **kw) if sharded else
                           decode_asr(self.vocab, model_outputs, **kw))
         return {"text": text, **optional}
+
+    def align(self, inputs: Union[str, bytes, np.ndarray, dict], chunks: Sequence[dict], *,
+              language: Optional[str] = None, task: Optional[str] = None, batch_size: Optional[int] = None,
+              return_language: bool = False) -> dict:
+        """Forced alignment (extension): when each word of a GIVEN transcript was said, and how strongly the model
+        agrees that it was. chunks: [{"timestamp": (t0, t1), "tokens": [text token ids]}, ...] — the callable's chunk
+        schema with token ids for text (t1 None: the end of the input); every chunk is one window of at most 30 s,
+        its samples zero padded, teacher-forced through the decoder (WhisperEngine.force_pass) with the
+        <|notimestamps|> prompt. Returns {"text", "chunks": word dicts as return_timestamps="word" builds them (times
+        shifted by the chunk's t0, "probability" as return_confidence defines it), "chunk_avg_logprob": per input
+        chunk the mean log-probability of its text tokens, None for an empty chunk}. Every argument is checked before
+        any GPU work; a chunk without tokens is not run. No prompts, no history processors, not sharded."""
+        st = self.gen.special
+        if not st.is_multilingual and (task is not None or language is not None):
+            raise ValueError("Cannot specify `task` or `language` for an English-only model.")
+        if dist.collective_path():
+            raise RuntimeError("align is not sharded: call it in a single process")
+        eng, sr = self.engine, self.sampling_rate
+        lang_id = self._lang_id(language)
+        tail = eng.prompt_tail(task, return_timestamps=False, language_given=lang_id is not None)
+        limit = eng.max_new_for(eng._prompt_len(tail))
+        for i, c in enumerate(chunks):  # what needs no audio is checked before the input is even decoded
+            t0, t1 = c["timestamp"]
+            if not 0 <= float(t0) or (t1 is not None and not float(t0) < float(t1)):
+                raise ValueError(f"align: chunk {i}: timestamp ({t0}, {t1}) needs 0 <= start < end")
+            if t1 is not None and float(t1) - float(t0) > CHUNK_SAMPLES / SAMPLE_RATE + 1e-9:
+                raise ValueError(f"align: chunk {i}: {float(t1) - float(t0):.3f} s is longer than one 30 s window")
+            if any(not 0 <= int(t) < st.eot for t in c["tokens"]):
+                raise ValueError(f"align: chunk {i}: token ids must be text tokens, below <|endoftext|> ({st.eot})")
+            if len(c["tokens"]) + 1 > limit:
+                raise ValueError(f"align: chunk {i}: {len(c['tokens'])} tokens and <|endoftext|> exceed the {limit} "
+                                 "positions the decoder has after the prompt")
+        wav = audio.load_input(inputs, sr, getattr(eng, "device", None))
+        if torch.is_tensor(wav):
+            wav = wav.float().cpu().numpy()
+        total = len(wav)
+        spans: List[Optional[tuple]] = []  # per chunk (first sample, samples, t0, tokens), None without tokens
+        for i, c in enumerate(chunks):
+            t0, t1 = c["timestamp"]
+            t0 = float(t0)
+            t1 = total / sr if t1 is None else float(t1)
+            toks = [int(t) for t in c["tokens"]]
+            if not (0 <= t0 < t1 and t1 <= total / sr + 1e-9):
+                raise ValueError(f"align: chunk {i}: timestamp ({t0}, {t1}) is not inside the input's "
+                                 f"{total / sr:.3f} s with 0 <= start < end")
+            if t1 - t0 > CHUNK_SAMPLES / SAMPLE_RATE + 1e-9:  # (an end of None: known only now)
+                raise ValueError(f"align: chunk {i}: {t1 - t0:.3f} s is longer than one 30 s window")
+            s0 = min(int(round(t0 * sr)), total - 1)
+            n = max(1, min(int(round(t1 * sr)), total, s0 + CHUNK_SAMPLES) - s0)
+            spans.append((s0, n, t0, toks) if toks else None)
+        run = [i for i, s in enumerate(spans) if s is not None]
+        B = eng.max_batch if batch_size is None else max(1, min(int(batch_size), eng.max_batch))
+        results: Dict[int, tuple] = {}  # chunk -> (language id, token times, token log-probabilities)
+        for b0 in range(0, len(run), B):
+            part = run[b0: b0 + B]
+            host = self._host_staging(0, len(part))
+            for j, i in enumerate(part):
+                s0, n = spans[i][:2]
+                host[j, :n] = torch.from_numpy(np.ascontiguousarray(wav[s0: s0 + n], np.float32))
+                host[j, n:] = 0
+            eng.wave[: len(part)].copy_(host)
+            eng.logmel(len(part))
+            eng.encode(len(part), row_map=False, seek=False)
+            res = eng.force_pass(len(part), tail, None if lang_id is None else [lang_id] * len(part),
+                                 [spans[i][3] for i in part], num_frames=[-(-spans[i][1] // 160) for i in part])
+            for j, i in enumerate(part):
+                results[i] = (res.lang_ids[j] if res.lang_ids else None, res.token_ts[j], res.token_lp[j])
+        P = eng._prompt_len(tail)
+        words: List[dict] = []
+        avg: List[Optional[float]] = []
+        for i, s in enumerate(spans):
+            if s is None:
+                avg.append(None)
+                continue
+            lang, ts, lp = results[i]
+            t0, toks = s[2], s[3]
+            # the word path of AsrStitcher.feed: a token spans the previous token's time to its own
+            pairs = [(round(float(ts[P + k - 1]) + t0, 2), round(float(ts[P + k]) + t0, 2)) for k in range(len(toks))]
+            name = None if lang is None else LANGUAGE_NAMES.get(self.vocab.id_to_token[lang][2:-2])
+            words.extend(collate_word_timestamps(self.vocab, toks, pairs, name, return_language,
+                                                 token_logprobs=lp[: len(toks)]))
+            avg.append(mean_logprob(lp[: len(toks)]))
+        text = "".join(self.vocab.decode(s[3]) for s in spans if s is not None)
+        return {"text": text, "chunks": words, "chunk_avg_logprob": avg}
 
     def _lang_id(self, language: Optional[str]) -> Optional[int]:
         if language is None:
