@@ -475,6 +475,22 @@ int tw_logits_sample_lp(const float* logits, int B, int ld_logits, const uint32_
  * One workgroup per row; the state is only read. */
 int tw_token_logprob(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
                      const TwSelectParams* params, const int* state, float* lp_out, int ld_lp, void* stream);
+/* Token alternatives: the k (1..TW_TOPK_MAX) best eligible ids of the step's processed scores, launched in front of
+ * the selection (tw_logits_select / _select_embed / tw_logits_sample / tw_logits_force / tw_beam_step) on the same
+ * logits, params and (still unchanged) state; the state is only read. Eligible: finite after the processors, and no
+ * text id when the timestamp rule fires (tw_logits_sample's set). Larger score first, ties to the lower id.
+ * Row b writes position q = state[b][TW_ST_NGEN] of ids_out int32[B][ld_out][k] and lp_out f32[B][ld_out][k] (nothing
+ * when q is outside [0, ld_out)): ids_out[b][q][j] = the j-th id, lp_out[b][q][j] = score - logsumexp(scores over the
+ * eligible set); a slot without a candidate, and every slot of a row with TW_ST_FINISHED, holds id -1, lp -inf.
+ * Columns [V, ld_logits) are never read. Raw scores (forced alignment): params with use_timestamps = 0 and
+ * n_begin_suppress = 0, suppress_bits NULL. Two launches: one workgroup per (row, vocab chunk) writes partial records
+ * into workspace (tw_token_topk_workspace_bytes(B) bytes, this call's own), one wave per row merges them.
+ * Errors: TW_ERR_ARG for k outside 1..TW_TOPK_MAX or a null pointer. */
+#define TW_TOPK_MAX 8
+size_t tw_token_topk_workspace_bytes(int rows);
+int tw_token_topk(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
+                  const TwSelectParams* params, const int* state, int k, int32_t* ids_out, float* lp_out, int ld_out,
+                  void* workspace, void* stream);
 /* state[b][TW_ST_NOSPEECH] (f32 bits) = softmax(logits[b][0:V])[token]: WhisperNoSpeechDetection's no_speech_prob
  * ($TF/generation/logits_process.py:2050-2112) from the logits at the <|startoftranscript|> position. */
 int tw_token_prob(const float* logits, int B, int ld_logits, int V, int token, int* state, void* stream);

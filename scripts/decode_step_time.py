@@ -4,7 +4,7 @@ detection, task token) + 128 generated tokens with EOS suppressed, i.e. 130 deco
 before, untimed. Prints one JSON line per (rows, mode).
 
     python scripts/decode_step_time.py [--rows 15 24 64] [--reps 3] [--fused 0 1] [--penalties 0 1] [--beams 12 5]
-                                       [--logprobs 0 1] [--seqbias 0 1]
+                                       [--logprobs 0 1] [--alternatives 0 8] [--seqbias 0 1]
 
 --fused 1: the decoder's layers as one persistent launch (tw_dec_fused) at every row count <= 32, 0: the launch chain
 (WhisperEngine.dec_fused_alone / dec_fused_max_rows overridden); with both, each row count runs both and reports
@@ -16,6 +16,9 @@ of every selection), 0: without; with both, the cost of the pre-pass is the diff
 0: without; the cost is the difference of the two lines.
 --logprobs 1: the passes run with token_logprobs (tw_token_logprob captured ahead of every selection; the beam pass
 with run_tlp / fin_tlp), 0: without; with both, the cost of the pre-kernel is the difference of the two lines.
+--alternatives K: the passes run with top_alternatives = K (tw_token_topk's two launches captured ahead of every
+selection; the beam pass with one launch over all its rows and the fin_tab gather after it), 0: without; the cost is
+the difference of the two lines.
 --beams W NB: also the beam pass of W windows x NB beams (one captured step per token: decoder step over W * NB rows,
 tw_beam_step), 128 tokens with EOS suppressed, per step from the pass's wall time.
 """
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--penalties", type=int, nargs="+", default=[0])
     ap.add_argument("--beams", type=int, nargs=2, default=None, metavar=("W", "NB"))
     ap.add_argument("--logprobs", type=int, nargs="+", default=[0])
+    ap.add_argument("--alternatives", type=int, nargs="+", default=[0])
     ap.add_argument("--seqbias", type=int, nargs="+", default=[0])
     a = ap.parse_args()
     dims = PRESETS["large-v3-turbo"]
@@ -70,9 +74,9 @@ def main():
         eng.encode(R)
         torch.cuda.synchronize()
         ref = {}  # per (penalties, seqbias) value: the first mode's tokens
-        for fz, ce, gs, pen, lpo, sbo in [(f, c, g, p, q, b) for f in a.fused for c in a.check_every
-                                          for g in a.graph_steps for p in a.penalties for q in a.logprobs
-                                          for b in a.seqbias]:
+        for fz, ce, gs, pen, lpo, sbo, alt in [(f, c, g, p, q, b, k) for f in a.fused for c in a.check_every
+                                               for g in a.graph_steps for p in a.penalties for q in a.logprobs
+                                               for b in a.seqbias for k in a.alternatives]:
             if fz and R > 32:
                 continue
             eng.dec_fused_alone = bool(fz)
@@ -82,6 +86,8 @@ def main():
             hk = {"repetition_penalty": 1.3, "no_repeat_ngram_size": 3} if pen else {}
             if lpo:
                 hk["token_logprobs"] = True
+            if alt:
+                hk["top_alternatives"] = alt
             if sbo:
                 hk.update(table)
             eng.decode_pass(R, tail, None, 128, check_every=ce, **hk)  # warm-up: graph captures
@@ -96,7 +102,8 @@ def main():
             loop_us = min(e0.elapsed_time(e1) * 1e3 / n for e0, e1, n, _ in eng.pass_events)
             eng.pass_events = None
             print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs, "penalties": pen,
-                              "logprobs": lpo, "seqbias": sbo, "loop_us_per_step": round(loop_us, 1)}),
+                              "logprobs": lpo, "alternatives": alt, "seqbias": sbo,
+                              "loop_us_per_step": round(loop_us, 1)}),
                   flush=True)
             assert all(len(t) == 128 for t in res.tokens)
             ref.setdefault((pen, sbo), res.tokens)
@@ -114,7 +121,7 @@ def main():
                                   "slope_us_per_step": round((best - b64) * 1e6 / 64, 1),
                                   "fixed_ms": round((b64 - 66 * (best - b64) / 64) * 1e3, 2)}), flush=True)
             print(json.dumps({"rows": R, "fused": fz, "check_every": ce, "graph_steps": gs, "penalties": pen,
-                              "logprobs": lpo, "seqbias": sbo, "pass_ms": round(best * 1e3, 2),
+                              "logprobs": lpo, "alternatives": alt, "seqbias": sbo, "pass_ms": round(best * 1e3, 2),
                               "step_us": round(best * 1e6 / 130, 1), "tokens_equal": res.tokens == ref[(pen, sbo)]}),
                   flush=True)
     if a.beams:
@@ -123,10 +130,12 @@ def main():
         eng.seek[:W] = 0
         eng.encode(W)
         torch.cuda.synchronize()
-        for pen, lpo in [(p, q) for p in a.penalties for q in a.logprobs]:
+        for pen, lpo, alt in [(p, q, k) for p in a.penalties for q in a.logprobs for k in a.alternatives]:
             hk = {"repetition_penalty": 1.3, "no_repeat_ngram_size": 3} if pen else {}
             if lpo:
                 hk["token_logprobs"] = True
+            if alt:
+                hk["top_alternatives"] = alt
             eng.beam_pass(W, nb, tail, None, 128, **hk)  # warm-up: graph capture
             torch.cuda.synchronize()
             best = 1e9
@@ -136,7 +145,7 @@ def main():
                 torch.cuda.synchronize()
                 best = min(best, time.perf_counter() - t0)
             print(json.dumps({"beam_windows": W, "num_beams": nb, "rows": W * nb, "penalties": pen, "logprobs": lpo,
-                              "pass_ms": round(best * 1e3, 2), "step_us": round(best * 1e6 / 130, 1)}), flush=True)
+                              "alternatives": alt, "pass_ms": round(best * 1e3, 2), "step_us": round(best * 1e6 / 130, 1)}), flush=True)
 
 
 if __name__ == "__main__":

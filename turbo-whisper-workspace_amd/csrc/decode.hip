@@ -1583,6 +1583,118 @@ extern "C" int tw_beam_step(const float* logits, int W, int ld_logits, const uin
   }
 }
 
+// =================================================================================================
+// Token alternatives: the k best eligible ids of a step's processed scores with their log-probabilities, in front of
+// the selection on the same logits, params and (only read) state.
+//   k_beam_partial<TW_TOPK_MAX>, renorm = 1   grid (B, NC): per chunk the top-8 masked text and timestamp candidates
+//                   and the logsumexp states of the allowed text / timestamp tokens (a workspace of its own)
+//   k_topk_final    grid B, one wave per row: merges the NC records, decides the timestamp rule as the selection does
+//                   (sel_rule_fires), and takes the top k of what is left under cand_better's order
+// A candidate list can hold ids whose score is -inf without a mask (a history processor wrote it): they are not
+// eligible and become sentinels here.
+// =================================================================================================
+__global__ __launch_bounds__(64) void k_topk_final(const BeamPart<TW_TOPK_MAX>* __restrict__ ws, int NC,
+                                                   TwSelectParams p, const int* __restrict__ state, int k,
+                                                   int32_t* __restrict__ ids_out, float* __restrict__ lp_out,
+                                                   int ld_out) {
+  TW_DEC_PRIO();
+  constexpr int K = TW_TOPK_MAX;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int* st = state + b * TW_STATE_STRIDE;
+  const int q = st[TW_ST_NGEN];
+  if (q < 0 || q >= ld_out) return;  // (uniform per block)
+  const size_t o = ((size_t)b * ld_out + q) * k;
+  if (st[TW_ST_FINISHED]) {
+    if (lane < k) {
+      ids_out[o + lane] = -1;
+      lp_out[o + lane] = -INFINITY;
+    }
+    return;
+  }
+  const BeamPart<K>* parts = ws + (size_t)b * NC;
+  // the pool: NC * K text and NC * K timestamp candidates, lane l holds entries l and l + 64 of each list
+  // (NC * K <= 128); static indices only, so it stays in registers
+  Cand pool[4];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int e = lane + 64 * u;
+    const bool ok = e < NC * K;
+    pool[u] = ok ? parts[e / K].t[e % K] : Cand{-INFINITY, 0x7fffffff};
+    pool[2 + u] = ok ? parts[e / K].s[e % K] : Cand{-INFINITY, 0x7fffffff};
+  }
+  float m_ts = -INFINITY, s_ts = 0.f, m_tx = -INFINITY, s_tx = 0.f;
+  for (int c = lane; c < NC; c += 64) {
+    lse_merge(m_ts, s_ts, parts[c].m_ts, parts[c].s_ts);
+    lse_merge(m_tx, s_tx, parts[c].m_tx, parts[c].s_tx);
+  }
+#pragma unroll
+  for (int x = 32; x > 0; x >>= 1) {
+    float m2 = __shfl_xor(m_ts, x, 64), s2 = __shfl_xor(s_ts, x, 64);
+    lse_merge(m_ts, s_ts, m2, s2);
+    m2 = __shfl_xor(m_tx, x, 64);
+    s2 = __shfl_xor(s_tx, x, 64);
+    lse_merge(m_tx, s_tx, m2, s2);
+  }
+  // the best text candidate decides the rule
+  Cand bt = cand_better(pool[1].v, pool[1].i, pool[0]) ? pool[1] : pool[0];
+  {
+    int bl = lane;
+    wave_best(bt.v, bt.i, bl);
+  }
+  const bool fire = sel_rule_fires(p, Best{bt.v, bt.i}, m_ts, s_ts);
+  float m = fire ? -INFINITY : m_tx, sm = fire ? 0.f : s_tx;
+  if (p.use_timestamps) lse_merge(m, sm, m_ts, s_ts);
+  const float lse = m + __logf(sm);
+  if (fire) pool[0] = pool[1] = Cand{-INFINITY, 0x7fffffff};
+  // k rounds of wave argmax over the pool; lane r keeps round r's winner
+  Cand mine{-INFINITY, 0x7fffffff};
+  for (int r = 0; r < k; ++r) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff, bq = -1;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool better = cand_better(pool[u].v, pool[u].i, Cand{bv, bi});
+      bv = better ? pool[u].v : bv;
+      bi = better ? pool[u].i : bi;
+      bq = better ? u : bq;
+    }
+    int bl = lane;
+    wave_best(bv, bi, bl);
+    const bool won = lane == bl;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) pool[u] = (won & (bq == u)) ? Cand{-INFINITY, 0x7fffffff} : pool[u];
+    if (lane == r) mine = Cand{bv, bi};
+  }
+  if (lane < k) {
+    const bool has = mine.v != -INFINITY;
+    ids_out[o + lane] = has ? mine.i : -1;
+    lp_out[o + lane] = has ? mine.v - lse : -INFINITY;
+  }
+}
+
+extern "C" size_t tw_token_topk_workspace_bytes(int rows) {
+  return (size_t)(rows > 0 ? rows : 0) * TW_SELECT_CHUNKS * sizeof(BeamPart<TW_TOPK_MAX>);
+}
+
+extern "C" int tw_token_topk(const float* logits, int B, int ld_logits, const uint32_t* suppress_bits,
+                             const TwSelectParams* params, const int* state, int k, int32_t* ids_out, float* lp_out,
+                             int ld_out, void* workspace, void* stream) {
+  TW_REQUIRE(logits && params && state && ids_out && lp_out && workspace && B > 0 && ld_out > 0,
+             "tw_token_topk: bad args");
+  TW_REQUIRE(k >= 1 && k <= TW_TOPK_MAX, "tw_token_topk: k=%d (1..%d)", k, TW_TOPK_MAX);
+  TW_REQUIRE(params->mode == 0, "tw_token_topk: generation steps (mode 0) only");
+  TW_REQUIRE(params->V > 0 && params->V <= ld_logits, "tw_token_topk: V=%d ld=%d", params->V, ld_logits);
+  TW_REQUIRE(params->n_begin_suppress >= 0 && params->n_begin_suppress <= 8, "tw_token_topk: begin_suppress");
+  static_assert(TW_SELECT_CHUNKS * TW_TOPK_MAX <= 128, "k_topk_final: two entries of each list per lane");
+  hipStream_t s = (hipStream_t)stream;
+  BeamPart<TW_TOPK_MAX>* ws = (BeamPart<TW_TOPK_MAX>*)workspace;
+  hipLaunchKernelGGL(k_beam_partial<TW_TOPK_MAX>, dim3(B, TW_SELECT_CHUNKS), dim3(256), 0, s, logits, ld_logits,
+                     suppress_bits, *params, state, ws, 1);
+  hipLaunchKernelGGL(k_topk_final, dim3(B), dim3(64), 0, s, ws, TW_SELECT_CHUNKS, *params, state, k, ids_out, lp_out,
+                     ld_out);
+  return tw_check_launch("tw_token_topk");
+}
+
 // Self-attention K/V reorder after a beam step: row r continues row src_rows[r]; positions [0, pos[r]) move.
 // In place, one launch for K and V: block (layer*head, position tile, K|V) stages the tile of every moved row's
 // source in LDS, then writes the destinations. Tiles are disjoint across blocks and a block reads all its sources

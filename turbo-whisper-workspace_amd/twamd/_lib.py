@@ -36,6 +36,7 @@ TW_HIST_MAX = 448   # tw_logits_history: ids per row history (prefix + generated
 TW_HIST_LANG = -1   # a prefix entry that reads the detected language, state[r][TW_ST_LANG]
 TW_SEQBIAS_MAX_ENTRIES = 256  # tw_logits_history_bias: sequence_bias + bad_words_ids entries
 TW_SEQBIAS_MAX_IDS = 16       # ids per entry
+TW_TOPK_MAX = 8               # tw_token_topk: alternatives per token
 
 # every symbol include/tw_whisper.h + include/tw_audio.h declare (tests check the .so exports all of them)
 EXPORTED = (
@@ -57,7 +58,7 @@ EXPORTED = (
     "tw_aac_adts_probe", "tw_aac_adts_decode", "tw_dec_fused", "tw_dec_fused_sync_bytes", "tw_dec_fused_supported",
     "tw_dec_fused_set_grid", "tw_dec_fused_set_acquire", "tw_dec_fused_set_probe", "tw_dec_fused_grid",
     "tw_dec_fused_xpart_bytes", "tw_logits_history", "tw_token_logprob", "tw_logits_sample_lp",
-    "tw_logits_history_bias", "tw_logits_force", "tw_align_cost",
+    "tw_logits_history_bias", "tw_logits_force", "tw_align_cost", "tw_token_topk_workspace_bytes", "tw_token_topk",
 )
 
 
@@ -195,6 +196,8 @@ _SIGS = {
     "tw_dtw": ([_P, _I, _I, _P, _P, _P], _I),
     "tw_attn_decode_cross_probs": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _U32, _I, _I, _P, _I, _I, _P], _I),
     "tw_beam_workspace_bytes": ([_I], ctypes.c_size_t),
+    "tw_token_topk_workspace_bytes": ([_I], ctypes.c_size_t),
+    "tw_token_topk": ([_P, _I, _I, _P, ctypes.POINTER(TwSelectParams), _P, _I, _P, _P, _I, _P, _P], _I),
     "tw_attn_decode_cross_grouped_ws_bytes": ([_I, _I], ctypes.c_size_t),
     "tw_attn_decode_self_tab": ([_P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P], _I),
     "tw_attn_decode_self_tab_masked": ([_P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P], _I),

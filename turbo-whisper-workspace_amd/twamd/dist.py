@@ -178,7 +178,7 @@ def transcribe_sharded(run_windows, wav: np.ndarray, windows: Sequence, device: 
     `run_windows(wav, windows[lo:hi]) -> List[List[int]]` on its own shard, then the results are all-gathered
     into the global window order. `timed`: run_windows returns tuples (tokens, per-token floats, ...) with that
     many float lanes after the tokens (True = 1: word timestamps' times; 2 with return_confidence's
-    log-probabilities behind them); every lane is gathered too and the tuples are returned."""
+    log-probabilities behind them; 2k more with return_alternatives = k); every lane is gathered too and the tuples are returned."""
     rank, ws = world()
     lo, hi = shard_range(len(windows), ws, rank)
     err: Optional[BaseException] = None
@@ -260,7 +260,8 @@ def assumed_state(vocab, outputs: Sequence[dict], lo: int, confidence: bool = Fa
 def shard_piece(vocab, outputs: Sequence[dict], lo: int, hi: int, **kw) -> tuple:
     """One shard's stitching: (assumed incoming state, its closed chunks, its final state)."""
     from .tokenizer import AsrStitcher
-    st0 = assumed_state(vocab, outputs, lo, bool(kw.get("confidence", False)))
+    # (alternatives ride in the same per-token value as the log-probabilities: the state has that key with either)
+    st0 = assumed_state(vocab, outputs, lo, bool(kw.get("confidence", False) or kw.get("alternatives", False)))
     sti = AsrStitcher(vocab, state=st0, **kw)
     for o in outputs[lo:hi]:
         sti.feed(o)
@@ -272,7 +273,7 @@ def merge_pieces(vocab, outputs: Sequence[dict], pieces: Sequence[tuple], bounds
     """The serial _decode_asr result from the shards' pieces (see above); returns (text, optional)."""
     from .tokenizer import AsrStitcher
     chunks: List[dict] = []
-    true = AsrStitcher.initial_state(confidence=bool(kw.get("confidence", False)))
+    true = AsrStitcher.initial_state(confidence=bool(kw.get("confidence", False) or kw.get("alternatives", False)))
     restitched = 0
     for (assumed, ch, final), (lo, hi) in zip(pieces, bounds):
         if assumed == true:
@@ -299,7 +300,7 @@ def stitch_sharded(vocab, outputs: Sequence[dict], group=None, force_collective:
     """decode_asr over every window (`outputs` in global order, identical on every rank), with the work split over
     the ranks: each stitches its own window shard, one all_gather_object brings the pieces to every rank, and every
     rank merges them (merge_pieces). kw: decode_asr's return_timestamps, return_language, time_precision,
-    segment_size, confidence."""
+    segment_size, confidence, alternatives."""
     from .tokenizer import decode_asr
     rank, ws = world()
     # without timestamps no window closes its chunk (the text accumulates until the end), so every shard after the

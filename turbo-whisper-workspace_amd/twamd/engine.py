@@ -194,6 +194,9 @@ class PassResult:
     # per row, one float per generated token: log_softmax(the step's processed scores)[token] (token_logprobs), the
     # terms sum_logprob sums; 0.0 for a pad after the row finished
     token_lp: Optional[List[List[float]]] = None
+    # per row, per generated token: the step's top alternatives as [(id, lp), ...], best first (top_alternatives);
+    # empty for a pad after the row finished
+    token_alt: Optional[List[List[List[Tuple[int, float]]]]] = None
 
 
 @dataclasses.dataclass(frozen=True)
@@ -213,25 +216,33 @@ class DecodeOptions:
     token_logprobs: every generated token's log-probability under the step's processed scores (output_scores: after
     the history and Whisper processors and the warpers, at temperature 1 — the terms of _retrieve_avg_logprobs) in
     PassResult.token_lp: tw_token_logprob in front of every greedy selection, tw_logits_sample_lp's and
-    tw_beam_step's per-token outputs (the terms of the sums those two return)."""
+    tw_beam_step's per-token outputs (the terms of the sums those two return).
+    top_alternatives: k in 1..TW_TOPK_MAX (0: off) — at every generated token the k best eligible ids of the step's
+    processed scores with their log-probabilities (tw_token_topk in front of the selection) in PassResult.token_alt.
+    On a sampled pass the list is the greedy one (temperature 1, before the top-k warper): its denominator is the
+    whole eligible set, token_lp's the kept top-50 set, so the two differ by a per-step constant."""
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
     length_penalty: float = 1.0
     token_logprobs: bool = False
     pre: Tuple[seqbias.Entry, ...] = ()
     post: Tuple[seqbias.Entry, ...] = ()
+    top_alternatives: int = 0
 
     @classmethod
     def make(cls, vocab: Optional[int] = None, eos: Optional[int] = None, *, repetition_penalty=None,
              no_repeat_ngram_size=None, length_penalty=None, token_logprobs=None, sequence_bias=None,
-             bad_words_ids=None) -> "DecodeOptions":
+             bad_words_ids=None, top_alternatives=None) -> "DecodeOptions":
         """From the public keywords; None is the neutral value. vocab / eos: the model's, for the entry checks."""
         pre = seqbias.sequence_bias_entries(sequence_bias, vocab) if sequence_bias is not None else []
         post = seqbias.bad_words_entries(bad_words_ids, eos, vocab) if bad_words_ids is not None else []
         seqbias.check_limits(pre, post)
+        k = int(top_alternatives or 0)
+        if not 0 <= k <= _lib.TW_TOPK_MAX:
+            raise ValueError(f"top_alternatives must be 0..{_lib.TW_TOPK_MAX}, got {top_alternatives!r}")
         return cls(float(repetition_penalty or 1.0), int(no_repeat_ngram_size or 0),
                    float(1.0 if length_penalty is None else length_penalty), bool(token_logprobs), tuple(pre),
-                   tuple(post))
+                   tuple(post), k)
 
     @property
     def history(self) -> bool:
@@ -245,8 +256,9 @@ class DecodeOptions:
 
     @property
     def graph_key(self) -> tuple:
-        """What a captured step bakes in: the history key and whether tw_token_logprob runs."""
-        return self.hist_key + (self.token_logprobs,)
+        """What a captured step bakes in: the history key, whether tw_token_logprob runs and tw_token_topk's k."""
+        # (k only when on: with the option off the key is the one it always was)
+        return self.hist_key + (self.token_logprobs,) + ((self.top_alternatives,) if self.top_alternatives else ())
 
 
 NO_OPTIONS = DecodeOptions()
@@ -393,6 +405,7 @@ class WhisperEngine:
         self._fused_xpart = (torch.empty(int(_lib.load().tw_dec_fused_xpart_bytes(32)) // 4, dtype=torch.float32,
                                          device=dev) if self._fused_dims else None)  # cross-attention slice states
         self._beam: Optional[dict] = None  # beam-search buffers, allocated on first use
+        self._alt: Optional[tuple] = None  # top_alternatives: (ids, lps, workspace), allocated on first use
         self._align: Optional[dict] = None  # token-level timestamps: alignment-head attention recording
         self._align_buf: Optional[torch.Tensor] = None
         self.suppress_bits = torch.zeros((V + 31) // 32, dtype=torch.int32, device=dev)
@@ -990,6 +1003,8 @@ class WhisperEngine:
                 _lib.call("tw_token_logprob", v.logits.data_ptr(), R, self.d.vocab, self.suppress_bits.data_ptr(),
                           ctypes.byref(params), v.state.data_ptr(), self.token_lp[v.r0:].data_ptr(),
                           self.token_lp.stride(0), v.stream.cuda_stream)
+            if self._opts.top_alternatives:  # the step's top candidates, from the same logits and state
+                self._topk(v.logits.data_ptr(), v.r0, R, params, v.stream.cuda_stream)
         if embed_next:
             L0 = self.w.dec[0]
             _lib.call("tw_logits_select_embed", v.logits.data_ptr(), R, self.d.vocab, self.suppress_bits.data_ptr(),
@@ -1002,6 +1017,47 @@ class WhisperEngine:
         _lib.call("tw_logits_select", v.logits.data_ptr(), R, self.d.vocab, self.suppress_bits.data_ptr(),
                   ctypes.byref(params), v.state.data_ptr(), v.tokens.data_ptr() if tokens else None,
                   v.tokens.shape[1], v.ids.data_ptr(), v.pos.data_ptr(), v.sel_ws.data_ptr(), v.stream.cuda_stream)
+
+    def _alt_alloc(self) -> None:
+        """top_alternatives' buffers, allocated at the first pass that asks for them (never inside a capture: _pass
+        calls this) and kept: ids / lps flat [max_rows * T * TW_TOPK_MAX], used as [rows][T][k] for the pass's k, and
+        tw_token_topk's workspace."""
+        if self._alt is None:
+            n = self.max_rows * self.d.max_target_positions * _lib.TW_TOPK_MAX
+            ws = int(_lib.load().tw_token_topk_workspace_bytes(self.max_rows))
+            self._alt = (torch.full((n,), -1, dtype=torch.int32, device=self.device),
+                         torch.full((n,), float("-inf"), dtype=torch.float32, device=self.device),
+                         torch.empty(ws, dtype=torch.uint8, device=self.device))
+
+    def _topk(self, logits_ptr: int, r0: int, R: int, params: _lib.TwSelectParams, stream: int, k: int = 0,
+              raw: bool = False) -> None:
+        """tw_token_topk for rows [r0, r0 + R) (logits_ptr: row r0's logits, row stride V) in front of their
+        selection; k defaults to the pass's top_alternatives. raw: no suppress mask (params are then neutral)."""
+        k = k or self._opts.top_alternatives
+        ids, lps, ws = self._alt
+        T = self.d.max_target_positions
+        _lib.call("tw_token_topk", logits_ptr, R, self.d.vocab, None if raw else self.suppress_bits.data_ptr(),
+                  ctypes.byref(params), self.state[r0:].data_ptr(), k, ids[r0 * T * k:].data_ptr(),
+                  lps[r0 * T * k:].data_ptr(), T, ws.data_ptr() + r0 * (ws.numel() // self.max_rows), stream)
+
+    def _alt_read(self, R: int, k: int, ngen: Sequence[int], rows: Optional[torch.Tensor] = None,
+                  cols: Optional[torch.Tensor] = None) -> List[List[List[Tuple[int, float]]]]:
+        """The pass's lists of rows [0, R): per row and generated token [(id, lp), ...] with the sentinel slots
+        dropped. rows / cols (int64 [R][n]): read token n of row r from [rows[r][n]][cols[r][n]] instead of [r][n]
+        (beam search: the row whose logits produced that token of the best hypothesis)."""
+        ids, lps, _ = self._alt
+        T = self.d.max_target_positions
+        n_rows = self.max_rows if rows is not None else R
+        ids = ids[: n_rows * T * k].view(n_rows, T, k)
+        lps = lps[: n_rows * T * k].view(n_rows, T, k)
+        if rows is not None:
+            ids, lps = ids[rows, cols], lps[rows, cols]
+        else:  # (only the positions the pass wrote come to the host)
+            n_max = max(ngen, default=0)
+            ids, lps = ids[:R, :n_max], lps[:R, :n_max]
+        ids, lps = ids.tolist(), lps.tolist()
+        return [[[(i, lp) for i, lp in zip(ids[r][n], lps[r][n]) if i >= 0] for n in range(ngen[r])]
+                for r in range(R)]
 
     def _hist_begin(self, R: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]], prefix_rows=None) -> None:
         """Start the pass's token history when its options run the pre-pass: rows [0, R) of the prefix buffer take
@@ -1248,6 +1304,8 @@ class WhisperEngine:
         All of it is back at its idle value when the pass ends, however it ends."""
         try:
             self._opts = opts
+            if opts.top_alternatives:
+                self._alt_alloc()
             if align is not None:
                 self._align_setup(*align)
             if row_map is not None:
@@ -1366,6 +1424,8 @@ class WhisperEngine:
             if opts.token_logprobs:
                 lp = self.token_lp[:R].tolist()
                 res.token_lp = [lp[r][: ngen[r]] for r in range(R)]
+            if opts.top_alternatives:
+                res.token_alt = self._alt_read(R, opts.top_alternatives, ngen)
             if align:
                 self._token_ts(res, num_frames)
         return res
@@ -1379,14 +1439,17 @@ class WhisperEngine:
 
     @on_engine_streams
     def force_pass(self, R: int, tail: Sequence[int], lang_ids: Optional[Sequence[int]],
-                   forced: Sequence[Sequence[int]], num_frames: Optional[Sequence[int]] = None) -> PassResult:
+                   forced: Sequence[Sequence[int]], num_frames: Optional[Sequence[int]] = None,
+                   top_alternatives: int = 0) -> PassResult:
         """Forced alignment of R encoded rows with given text: forced[r] (text token ids) followed by
         <|endoftext|> is fed through the decoder from the prompt [SOT, (lang), *tail] (the language detected when
         lang_ids is None on a multilingual model, as decode_pass), teacher-forced on the device: every step after
         the prompt is decoder_step + tw_logits_force, captured once and replayed, with no finished check and no host
         synchronisation until the last step is queued. Returns tokens (the forced ids + EOT), token_lp (the model's
         own log-probability of each, raw logits: nothing is chosen, so no processor runs) and token_ts in _token_ts's
-        layout (prompt zeros, one time per token).
+        layout (prompt zeros, one time per token). top_alternatives = k (1..TW_TOPK_MAX): token_alt holds, per given
+        token, the model's k best ids under the same raw logits (tw_token_topk in front of tw_logits_force, in both
+        captured graphs): the given token is in its list exactly when its rank is at most k, with token_lp's value.
 
         Unlike _token_ts, which standardises a batch over its padded length, every row's times come from that row's
         own fed tokens (len(forced[r])) and its own frame crop (num_frames[r] // 2, at most 1500): a chunk's alignment
@@ -1408,6 +1471,14 @@ class WhisperEngine:
         if num_frames is not None and len(num_frames) != R:
             raise ValueError("force_pass: one num_frames per row")
         detect = st.is_multilingual and lang_ids is None
+        k_alt = int(top_alternatives or 0)
+        if not 0 <= k_alt <= _lib.TW_TOPK_MAX:
+            raise ValueError(f"top_alternatives must be 0..{_lib.TW_TOPK_MAX}, got {top_alternatives!r}")
+        if k_alt:
+            self._alt_alloc()
+            # neutral params: the raw logits, as tw_logits_force (max_new is not read: the captured steps hold no length)
+            raw = self._select_params(0, 1, use_timestamps=False)
+            raw.n_begin_suppress = 0
         with self._pass(NO_OPTIONS, align=(R, P, max_len)):
             self._dec_context()
             self.stream.wait_event(self._enc_ev[self._slot])  # the cross-K/V of this slot is written
@@ -1417,20 +1488,25 @@ class WhisperEngine:
             self._force_ids[:R, :max_len] = torch.from_numpy(table).to(self.device)
             self._force_len[:R] = torch.tensor(lens, dtype=torch.int32, device=self.device)
 
+            def score() -> None:  # (the alternatives first: tw_logits_force advances the state they read)
+                if k_alt:
+                    self._topk(self.logits.data_ptr(), 0, R, raw, self._s, k_alt, raw=True)
+                self._force(R)
+
             def prompt() -> None:  # the prompt steps and the first given token (scored from the last prompt token)
                 self._prompt_phase(R, R, 0, lang_ids, tail, max_len)
                 self.decoder_step(R)
-                self._force(R)
+                score()
 
             def step() -> None:  # feeds the token the previous step committed, commits (and scores) the next
                 self.decoder_step(R)
-                self._force(R)
+                score()
 
             # both graphs are captured before anything is replayed (a capture synchronises the device): from the
             # prompt to the last step the host only queues
             gp = gs = None
             if self.use_graphs:
-                key = ("force", R, self._slot, self._align_key(), self._dec_ctx)
+                key = ("force", R, self._slot, self._align_key(), self._dec_ctx) + ((k_alt,) if k_alt else ())
                 if self.prompt_graph and (detect or not st.is_multilingual):
                     gp = self._captured(key + ("prompt", tuple(int(t) for t in tail)), prompt)
                 if max_len > 1:
@@ -1454,6 +1530,8 @@ class WhisperEngine:
                              self.state[:R, _lib.TW_ST_LANG].tolist() if detect else
                              None if lang_ids is None else list(lang_ids))
             res.token_lp = [lps[r][: lens[r]] for r in range(R)]
+            if k_alt:
+                res.token_alt = self._alt_read(R, k_alt, lens)
             res.token_ts = [np.concatenate([np.zeros(P, np.float32), t]) for t in ts]
         return res
 
@@ -1622,6 +1700,8 @@ class WhisperEngine:
                 if steps == 0 and ns_owed:
                     self._no_speech(R, no_speech_token)
                 self._history(0, R, self.stream)
+                if opts.top_alternatives:  # (the greedy list: temperature 1, before the top-k warper)
+                    self._topk(self.logits.data_ptr(), 0, R, params, self._s)
                 _lib.call("tw_logits_sample_lp", self.logits.data_ptr(), R, self.d.vocab,
                           self.suppress_bits.data_ptr(), ctypes.byref(params), float(temperature), int(top_k),
                           int(seed) & 0xFFFFFFFFFFFFFFFF, keys.data_ptr(), self.state.data_ptr(),
@@ -1644,6 +1724,8 @@ class WhisperEngine:
             if token_lp is not None:
                 lp = token_lp[:R].tolist()
                 res.token_lp = [lp[r][: ngen[r]] for r in range(R)]
+            if opts.top_alternatives:
+                res.token_alt = self._alt_read(R, opts.top_alternatives, ngen)
             if align:
                 self._token_ts(res, num_frames)
         return res
@@ -1707,6 +1789,7 @@ class WhisperEngine:
         if prefix is not None:
             prefix = (per_row(prefix[0]), per_row(prefix[1]))
         tlp = opts.token_logprobs
+        k_alt = opts.top_alternatives
         # rows w * nb + j share window w's cross K/V. The self-attention K/V position table: every row starts on its
         # own history; tw_beam_step points a continuing beam at its source's rows (no K/V copy: the reorder moved
         # ~550 MB per step at 60 rows)
@@ -1737,7 +1820,7 @@ class WhisperEngine:
             bst = _lib.TwBeamState(bb["run_score"].data_ptr(), bb["fin_score"].data_ptr(), bb["fin_flag"].data_ptr(),
                                    bb["fin_len"].data_ptr(), bb["fin_tokens"].data_ptr(), bb["win"].data_ptr(),
                                    bb["src_rows"].data_ptr(), bb["kv_tab"].data_ptr(),
-                                   bb["fin_tab"].data_ptr() if align else None,
+                                   bb["fin_tab"].data_ptr() if align or k_alt else None,
                                    bb["run_lp"].data_ptr() if lps else None,
                                    bb["fin_lp"].data_ptr() if lps else None,
                                    self.token_lp.data_ptr() if tlp else None,  # (run_tlp: beside tokens)
@@ -1748,6 +1831,8 @@ class WhisperEngine:
                 if after_decoder is not None:
                     after_decoder()
                 self._history(0, R, self.stream, to_logprobs=True)
+                if k_alt:  # every row's list at this step (a per-row shift of the scores does not change it)
+                    self._topk(self.logits.data_ptr(), 0, R, sel, self._s)
                 _lib.call("tw_beam_step", self.logits.data_ptr(), W, self.d.vocab, self.suppress_bits.data_ptr(),
                           ctypes.byref(sel), ctypes.byref(bp), ctypes.byref(bst), self.state.data_ptr(),
                           self.tokens.data_ptr(), self.ids.data_ptr(), self.pos.data_ptr(), bb["ws"].data_ptr(),
@@ -1791,6 +1876,15 @@ class WhisperEngine:
             if tlp:
                 flp = bb["fin_tlp"][:R:nb].tolist()
                 res.token_lp = [flp[w][: flen[w]] for w in range(W)]
+            if k_alt and max(flen, default=0) > 0:
+                # token n of a best hypothesis was chosen from the logits of the row that fed position P + n - 1
+                # (fin_tab; the last prompt position for n = 0, where every row of the window is a copy), at step n
+                P, n_max = self._prompt_len(tail, prefix), max(flen)
+                rows = bb["fin_tab"][:R:nb, P - 1: P - 1 + n_max].long()
+                cols = torch.arange(n_max, device=dev)[None, :].expand(W, n_max)
+                res.token_alt = self._alt_read(W, k_alt, flen, rows, cols)
+            elif k_alt:
+                res.token_alt = [[] for _ in range(W)]
             if align:
                 self._token_ts(res, num_frames, nb)
         return res
@@ -1886,7 +1980,8 @@ class WhisperEngine:
         options: DecodeOptions.make's keywords, checked before any work is queued and applied to every pass (each seek
         pass starts a new history: its prompt + what it generated). With token_logprobs, last_pass_logprobs is
         parallel to last_passes and last_token_logprobs to the returned segment tokens (else both None); the tokens are
-        those of the same call without it."""
+        those of the same call without it. With top_alternatives = k, last_pass_alternatives / last_token_alternatives
+        hold, the same way, every token's list of up to k (id, log-probability) candidates, best first."""
         if slot is not None:
             self.use_slot(slot)
         if pre_encoded and n_chunks > self.max_batch:
@@ -1950,6 +2045,10 @@ class WhisperEngine:
         # token_logprobs: per chunk the kept tokens' log-probabilities (beside segs) and every pass's (beside passes_raw)
         tlps: List[List[float]] = [[] for _ in range(n_chunks)]
         passes_lp: List[List[List[float]]] = [[] for _ in range(n_chunks)]
+        # top_alternatives: the same two, each token's list of (id, lp)
+        k_alt = opts.top_alternatives
+        talts: List[list] = [[] for _ in range(n_chunks)]
+        passes_alt: List[list] = [[] for _ in range(n_chunks)]
         while any(seek[i] < maxf[i] for i in range(n_chunks)):
             rows = [i for i in range(n_chunks) if seek[i] < maxf[i]]
             per = self.max_batch if num_beams == 1 else min(self.max_batch, self.max_rows // num_beams)
@@ -1994,7 +2093,7 @@ class WhisperEngine:
                 nf_part = None if num_frames is None else [int(num_frames[i]) - seek[i] for i in part]
                 if fb is not None:
                     pre = pre_encoded and passes == 0
-                    toks_f, skip_f, lang_f, temp_f, nb_left, ts_f, lp_f = self._fallback_pass(
+                    toks_f, skip_f, lang_f, temp_f, nb_left, ts_f, lp_f, alt_f = self._fallback_pass(
                         R, tail, given, mnew, return_timestamps, fb, [window_offset + i for i in part], passes,
                         enc_row0=b0 if pre else 0, r_enc=n_chunks if pre else R, prefix=pfx, num_beams=num_beams,
                         align=word_timestamps, num_frames=nf_part, opts=opts)
@@ -2007,6 +2106,8 @@ class WhisperEngine:
                         passes_raw[i].append(list(toks_f[j]))
                         if token_logprobs:
                             passes_lp[i].append(list(lp_f[j]))
+                        if k_alt:
+                            passes_alt[i].append(list(alt_f[j]))
                         snf = min(maxf[i] - seek[i], N_FRAMES)  # seek_num_frames
                         if skip_f[j]:  # generate(): seek += seek_num_frames, nothing kept
                             seek[i] += snf
@@ -2018,6 +2119,8 @@ class WhisperEngine:
                             self._add_times(tts[i], ts_f[j], prompt_len + L, len(seg_tokens), seek[i])
                         if token_logprobs:  # (the kept tokens are a prefix of the pass's)
                             tlps[i].extend(lp_f[j][: len(seg_tokens)])
+                        if k_alt:
+                            talts[i].extend(alt_f[j][: len(seg_tokens)])
                         seek[i] += offset
                     continue
                 if num_beams > 1:  # pre-encoded first pass: this part's windows sit at encoder rows b0..
@@ -2044,6 +2147,9 @@ class WhisperEngine:
                     if token_logprobs:
                         passes_lp[i].append(list(res.token_lp[j]))
                         tlps[i].extend(res.token_lp[j][: len(seg_tokens)])
+                    if k_alt:
+                        passes_alt[i].append(list(res.token_alt[j]))
+                        talts[i].extend(res.token_alt[j][: len(seg_tokens)])
                     seek[i] += offset
             passes += 1
             if max_passes is not None and passes >= max_passes:
@@ -2055,6 +2161,8 @@ class WhisperEngine:
         self.last_token_timestamps = tts if word_timestamps else None
         self.last_pass_logprobs = passes_lp if token_logprobs else None
         self.last_token_logprobs = tlps if token_logprobs else None
+        self.last_pass_alternatives = passes_alt if k_alt else None
+        self.last_token_alternatives = talts if k_alt else None
         return segs
 
     @staticmethod
@@ -2073,7 +2181,8 @@ class WhisperEngine:
         temperatures run out. Returns per row the kept sequence (EOS removed), should_skip, the language ids, each
         row's last temperature, the beam count left for the rest of the generate() call and (align) each row's token
         times from the round that decided it (its round's batch: _postprocess_outputs per round, :1051) and
-        (token_logprobs) the kept sequence's per-token log-probabilities, from that same round.
+        (token_logprobs) the kept sequence's per-token log-probabilities, from that same round, and (top_alternatives)
+        its per-token alternatives.
         Bug-compatible with transformers: needs_fallback / should_skip are written at the row's position in the
         CURRENT (shrinking) subset, and the main loop reads should_skip by batch position (:1074-1088, :879); the
         no-speech probability of a retry round is read by subset position from the whole pass's (the processor's
@@ -2095,6 +2204,7 @@ class WhisperEngine:
         row_ts: List[Optional[np.ndarray]] = [None] * R
         row_lp: List[Optional[List[float]]] = [None] * R
         token_logprobs = opts.token_logprobs
+        row_alt: List[Optional[list]] = [None] * R
         for fi, t in enumerate(temps):
             do_sample = t is not None and t > 0.0
             if do_sample:
@@ -2132,13 +2242,15 @@ class WhisperEngine:
                 seqs[idx[j]] = seq
                 if token_logprobs:
                     row_lp[idx[j]] = list(res.token_lp[j][: len(seq)])
+                if opts.top_alternatives:
+                    row_alt[idx[j]] = list(res.token_alt[j][: len(seq)])
                 if needs:
                     new_idx.append(idx[j])
             idx = new_idx
             if not idx or fi == len(temps) - 1:
                 break
         return (seqs, skip, langs if langs is not None else [None] * R, final_t, nb, (row_ts if align else None),
-                (row_lp if token_logprobs else None))
+                (row_lp if token_logprobs else None), (row_alt if opts.top_alternatives else None))
 
     @on_engine_streams
     def run_batches(self, sizes: Sequence[int], load=None, batch_kwargs: Optional[Sequence[dict]] = None,
@@ -2174,6 +2286,8 @@ class WhisperEngine:
         self.batch_prefixes = []
         self.batch_pass_logprobs = []  # (generate(token_logprobs=True): last_pass_logprobs / last_token_logprobs)
         self.batch_token_logprobs = []
+        self.batch_pass_alternatives = []  # (generate(top_alternatives=k): last_pass_alternatives / last_token_alternatives)
+        self.batch_token_alternatives = []
         overlap = self.overlap  # False: encoder and decoder strictly in turn
         if sizes:
             prefetch(0)
@@ -2197,5 +2311,7 @@ class WhisperEngine:
             self.batch_prefixes.append(self.last_pass_prefixes)
             self.batch_pass_logprobs.append(self.last_pass_logprobs)
             self.batch_token_logprobs.append(self.last_token_logprobs)
+            self.batch_pass_alternatives.append(self.last_pass_alternatives)
+            self.batch_token_alternatives.append(self.last_token_alternatives)
         self.use_slot(0)
         return out

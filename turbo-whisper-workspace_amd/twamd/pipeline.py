@@ -19,7 +19,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import audio, dist, seqbias
+from . import _lib, audio, dist, seqbias
 from .config import PRESETS, GenerationSettings, WhisperDims
 from .engine import WhisperEngine
 from .engine_f32 import WhisperEngineF32
@@ -34,6 +34,16 @@ _NAME_TO_CODE = {v: k for k, v in LANGUAGE_NAMES.items()}
 PIPELINE_DEFAULT_NUM_BEAMS = 5
 PIPELINE_DEFAULT_MAX_NEW_TOKENS = 256
 _GLOBAL_DEFAULT_MAX_LENGTH = 20  # GenerationConfig's own max_length default
+
+
+def _alternatives_arg(k, word: bool, name: str) -> int:
+    """return_alternatives / alternatives checked: 0 (off) or 1..TW_TOPK_MAX (8), and only with word timestamps."""
+    top = _lib.TW_TOPK_MAX
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) <= top:
+        raise ValueError(f"`{name}` must be an integer from 0 (off) to {top}, got {k!r}")
+    if k and not word:
+        raise ValueError(f"`{name}` needs return_timestamps=\"word\": the alternatives are returned per word")
+    return int(k)
 
 
 def resolve_decode(gen: GenerationSettings, gk: Dict[str, Any]) -> Dict[str, Any]:
@@ -126,15 +136,19 @@ class TurboTranscriber:
     def __call__(self, inputs: Union[str, bytes, np.ndarray, dict], *, chunk_length_s: float = 0,
                  stride_length_s=None, batch_size: int = 1, generate_kwargs: Optional[Dict[str, Any]] = None,
                  return_timestamps: Union[bool, str] = False, return_language: bool = False,
-                 return_confidence: bool = False, **kwargs) -> dict:
+                 return_confidence: bool = False, return_alternatives: int = 0, **kwargs) -> dict:
         """The HF ASR pipeline call. return_confidence (extension): the log-probability of every generated token
         under its step's processed scores (WhisperEngine.generate(token_logprobs=True)) rides through the stitching
         and comes out as each word's "probability" (return_timestamps="word": the mean of exp(lp) over the word's
         tokens, openai-whisper's definition), each chunk's "avg_logprob" (return_timestamps=True) or the result's
         "avg_logprob"; text, timestamps and chunks are those of the call without it. last_window_pass_logprobs then
-        sits beside last_window_passes."""
+        sits beside last_window_passes. return_alternatives = k (extension, 1..8, with return_timestamps="word"):
+        every word dict gains "alternatives", one list per token of the word, each up to k dicts {"id", "text",
+        "logprob"} — the model's k best candidates at that token under the step's processed scores, best first
+        (WhisperEngine.generate(top_alternatives=k)); every other value is that of the call without it."""
         word = return_timestamps == "word"
         conf = bool(return_confidence)
+        n_alt = _alternatives_arg(return_alternatives, word, "return_alternatives")
         if return_timestamps == "char":
             raise ValueError("Whisper cannot return `char` timestamps, only word level or segment level timestamps.")
         gk = dict(generate_kwargs or {})
@@ -206,7 +220,7 @@ class TurboTranscriber:
             return self._long_form(wav, task=task, language=language, return_timestamps=return_timestamps,
                                    return_language=return_language, max_new_tokens=max_new_tokens,
                                    num_beams=num_beams, max_passes=max_passes, fallback=fallback, condition=cond,
-                                   prompt=prompt, history=hist, confidence=conf)
+                                   prompt=prompt, history=hist, confidence=conf, alternatives=n_alt)
         else:
             windows = [Window(0, len(wav), 0, 0, True)]
             with_stride = False
@@ -225,7 +239,8 @@ class TurboTranscriber:
                       **({"prompt": prompt} if prompt else {}),
                       **({"history": hist} if hist else {}),
                       **({"group": batch_size} if grouped else {}),
-                      **({"token_logprobs": True} if conf else {}))
+                      **({"token_logprobs": True} if conf else {}),
+                      **({"top_alternatives": n_alt} if n_alt else {}))
             if word:  # token times ride along as floats after the tokens (one all-gather carries both)
                 nf = [-(-min(x.length, CHUNK_SAMPLES) // 160) for x in ws]
                 toks = self.transcribe_windows(w, ws, word_timestamps=True, num_frames=nf, **kw)
@@ -236,10 +251,16 @@ class TurboTranscriber:
             if conf:  # the log-probabilities ride the same way (0.0 beside the batch's right padding)
                 lanes.append([list(lp) + [0.0] * (len(t) - len(lp))
                               for t, lp in zip(toks, self.last_window_token_logprobs)])
+            if n_alt:  # 2k more lanes: slot j's ids (exact in f32) and log-probabilities; empty slots -1 / -inf
+                for j in range(n_alt):
+                    for f, empty in ((0, -1.0), (1, float("-inf"))):
+                        lanes.append([[float(a[j][f]) if j < len(a) else empty for a in alts]
+                                      + [empty] * (len(t) - len(alts))
+                                      for t, alts in zip(toks, self.last_window_token_alternatives)])
             return [tuple(x) for x in zip(toks, *lanes)] if lanes else toks
 
         # one window shard per rank + one all-gather of the token arrays (twamd.dist); plain call on 1 GPU
-        n_lanes = int(word) + int(conf)
+        n_lanes = int(word) + int(conf) + 2 * n_alt
         outputs = dist.transcribe_sharded(run, wav, windows, timed=n_lanes) if sharded else run(wav, windows)
         model_outputs = []
         for w, toks in zip(windows, outputs):
@@ -249,7 +270,11 @@ class TurboTranscriber:
                 if word:
                     o["token_timestamps"] = fl[0]
                 if conf:
-                    o["token_logprobs"] = fl[-1]
+                    o["token_logprobs"] = fl[int(word)]
+                if n_alt:
+                    al = fl[n_lanes - 2 * n_alt:]
+                    o["token_alternatives"] = [[[int(al[2 * j][n]), al[2 * j + 1][n]] for j in range(n_alt)
+                                                if al[2 * j][n] >= 0] for n in range(len(toks))]
             o["tokens"] = toks
             if with_stride:
                 sr = self.sampling_rate
@@ -257,7 +282,7 @@ class TurboTranscriber:
             model_outputs.append(o)
         kw = dict(return_timestamps="word" if word else bool(return_timestamps), return_language=return_language,
                   time_precision=time_precision(self.engine.d.max_source_positions),
-                  **({"confidence": True} if conf else {}))
+                  **({"confidence": True} if conf else {}), **({"alternatives": True} if n_alt else {}))
         # sharded: every rank stitches its own windows and the pieces are merged (dist.stitch_sharded: the serial
         # _decode_asr result, without rank 0 walking every window of the call)
         text, optional = (dist.stitch_sharded(self.vocab, model_outputs, **kw) if sharded else
@@ -266,7 +291,7 @@ class TurboTranscriber:
 
     def align(self, inputs: Union[str, bytes, np.ndarray, dict], chunks: Sequence[dict], *,
               language: Optional[str] = None, task: Optional[str] = None, batch_size: Optional[int] = None,
-              return_language: bool = False) -> dict:
+              return_language: bool = False, alternatives: int = 0) -> dict:
         """Forced alignment (extension): when each word of a GIVEN transcript was said, and how strongly the model
         agrees that it was. chunks: [{"timestamp": (t0, t1), "tokens": [text token ids]}, ...] — the callable's chunk
         schema with token ids for text (t1 None: the end of the input); every chunk is one window of at most 30 s,
@@ -274,8 +299,12 @@ class TurboTranscriber:
         <|notimestamps|> prompt. Returns {"text", "chunks": word dicts as return_timestamps="word" builds them (times
         shifted by the chunk's t0, "probability" as return_confidence defines it), "chunk_avg_logprob": per input
         chunk the mean log-probability of its text tokens, None for an empty chunk}. Every argument is checked before
-        any GPU work; a chunk without tokens is not run. No prompts, no history processors, not sharded."""
+        any GPU work; a chunk without tokens is not run. No prompts, no history processors, not sharded.
+        alternatives = k (1..8): every word dict gains "alternatives" as return_alternatives defines it, from
+        force_pass's raw-logit lists — the model's own k best candidates at every given token; a given token missing
+        from its list was not among them."""
         st = self.gen.special
+        n_alt = _alternatives_arg(alternatives, True, "alternatives")
         if not st.is_multilingual and (task is not None or language is not None):
             raise ValueError("Cannot specify `task` or `language` for an English-only model.")
         if dist.collective_path():
@@ -327,9 +356,11 @@ class TurboTranscriber:
             eng.logmel(len(part))
             eng.encode(len(part), row_map=False, seek=False)
             res = eng.force_pass(len(part), tail, None if lang_id is None else [lang_id] * len(part),
-                                 [spans[i][3] for i in part], num_frames=[-(-spans[i][1] // 160) for i in part])
+                                 [spans[i][3] for i in part], num_frames=[-(-spans[i][1] // 160) for i in part],
+                                 **({"top_alternatives": n_alt} if n_alt else {}))
             for j, i in enumerate(part):
-                results[i] = (res.lang_ids[j] if res.lang_ids else None, res.token_ts[j], res.token_lp[j])
+                results[i] = (res.lang_ids[j] if res.lang_ids else None, res.token_ts[j], res.token_lp[j],
+                              res.token_alt[j] if n_alt else None)
         P = eng._prompt_len(tail)
         words: List[dict] = []
         avg: List[Optional[float]] = []
@@ -337,13 +368,14 @@ class TurboTranscriber:
             if s is None:
                 avg.append(None)
                 continue
-            lang, ts, lp = results[i]
+            lang, ts, lp, alts = results[i]
             t0, toks = s[2], s[3]
             # the word path of AsrStitcher.feed: a token spans the previous token's time to its own
             pairs = [(round(float(ts[P + k - 1]) + t0, 2), round(float(ts[P + k]) + t0, 2)) for k in range(len(toks))]
             name = None if lang is None else LANGUAGE_NAMES.get(self.vocab.id_to_token[lang][2:-2])
             words.extend(collate_word_timestamps(self.vocab, toks, pairs, name, return_language,
-                                                 token_logprobs=lp[: len(toks)]))
+                                                 token_logprobs=lp[: len(toks)],
+                                                 token_alternatives=alts[: len(toks)] if n_alt else None))
             avg.append(mean_logprob(lp[: len(toks)]))
         text = "".join(self.vocab.decode(s[3]) for s in spans if s is not None)
         return {"text": text, "chunks": words, "chunk_avg_logprob": avg}
@@ -360,7 +392,8 @@ class TurboTranscriber:
         return lt[tok]
 
     def _long_form(self, wav, *, task, language, return_timestamps, return_language, max_new_tokens, num_beams,
-                   max_passes, fallback, condition=False, prompt=None, history=None, confidence=False) -> dict:
+                   max_passes, fallback, condition=False, prompt=None, history=None, confidence=False,
+                   alternatives=0) -> dict:
         """An input longer than 30 s without chunk_length_s: the pipeline hands generate() the features of the whole
         input (feature extractor with truncation=False, padding="longest", $TF/pipelines/automatic_speech_recognition
         .py:450-457) and generate() runs its seek loop over all of them (generation_whisper.py:647-968: is_shortform
@@ -381,6 +414,8 @@ class TurboTranscriber:
                 kw.update(word_timestamps=True, num_frames=[-(-int(x.shape[0]) // 160)])
             if confidence:
                 kw.update(token_logprobs=True)
+            if alternatives:
+                kw.update(top_alternatives=alternatives)
             toks = eng.generate(1, task=task, lang_ids=None if lang_id is None else [lang_id],
                                 max_new_tokens=max_new_tokens, return_timestamps=True, num_beams=num_beams,
                                 max_passes=max_passes, condition_on_prev_tokens=condition, **kw)[0]
@@ -397,10 +432,14 @@ class TurboTranscriber:
             self.last_window_pass_logprobs = list(eng.last_pass_logprobs)
             self.last_window_token_logprobs = list(eng.last_token_logprobs)
             out["token_logprobs"] = eng.last_token_logprobs[0]
+        if alternatives:
+            self.last_window_token_alternatives = list(eng.last_token_alternatives)
+            out["token_alternatives"] = eng.last_token_alternatives[0]
         text, optional = decode_asr(self.vocab, [out], return_timestamps="word" if word else bool(return_timestamps),
                                     return_language=return_language,
                                     time_precision=time_precision(self.engine.d.max_source_positions),
-                                    **({"confidence": True} if confidence else {}))
+                                    **({"confidence": True} if confidence else {}),
+                                    **({"alternatives": True} if alternatives else {}))
         return {"text": text, **optional}
 
     def transcribe_windows(self, wav: np.ndarray, windows: Sequence[Window], task: Optional[str],
@@ -410,7 +449,7 @@ class TurboTranscriber:
                            max_passes: Optional[int] = None, fallback: Optional[FallbackConfig] = None,
                            window_base: int = 0, condition_on_prev_tokens: bool = False,
                            prompt: Optional[dict] = None, history: Optional[dict] = None,
-                           token_logprobs: bool = False) -> List[List[int]]:
+                           token_logprobs: bool = False, top_alternatives: int = 0) -> List[List[int]]:
         """Log-mel + generate for every window; returns per-window token sequences (generate() output,
         right-padded with the pad token within each engine batch, as the HF batch output is). Batches of
         max_batch windows go through WhisperEngine.run_batches: batch k+1 is encoded while batch k decodes.
@@ -427,7 +466,7 @@ class TurboTranscriber:
 
         token_logprobs: every batch's generate() also records the tokens' log-probabilities
         (last_window_pass_logprobs beside last_window_passes, last_window_token_logprobs beside the returned tokens,
-        unpadded).
+        unpadded). top_alternatives: likewise every token's alternatives (last_window_token_alternatives).
 
         wav: a host array, or a torch tensor (a rank's copy of the broadcast waveform, in device memory)."""
         eng = self.engine
@@ -469,7 +508,8 @@ class TurboTranscriber:
                               **({"fallback": fallback, "window_offset": window_base} if fallback is not None else {}),
                               **({"condition_on_prev_tokens": True} if condition_on_prev_tokens else {}),
                               **(prompt or {}), **(history or {}),
-                              **({"token_logprobs": True} if token_logprobs else {}))
+                              **({"token_logprobs": True} if token_logprobs else {}),
+                              **({"top_alternatives": int(top_alternatives)} if top_alternatives else {}))
         out: List[List[int]] = []
         for seqs in res:
             out.extend(pad_right(seqs, self.gen.special.eot))
@@ -482,6 +522,8 @@ class TurboTranscriber:
         if token_logprobs:
             self.last_window_pass_logprobs = [p for bp in eng.batch_pass_logprobs for p in bp]
             self.last_window_token_logprobs = [t for bt in eng.batch_token_logprobs for t in bt]
+        if top_alternatives:
+            self.last_window_token_alternatives = [t for bt in eng.batch_token_alternatives for t in bt]
         return out
 
     @staticmethod

@@ -289,9 +289,11 @@ def _merge_punctuations(words, tokens, indices, prepended="\"'“¡¿([{-", appe
 
 
 def collate_word_timestamps(vocab: "WhisperVocab", tokens: List[int], token_timestamps, language: Optional[str],
-                            return_language: bool, token_logprobs: Optional[Sequence[float]] = None) -> List[dict]:
+                            return_language: bool, token_logprobs: Optional[Sequence[float]] = None,
+                            token_alternatives: Optional[Sequence[Sequence]] = None) -> List[dict]:
     """_collate_word_timestamps + _combine_tokens_into_words (:1273-1312). token_logprobs (one per token): every
-    word dict also gets "probability" (word_probabilities)."""
+    word dict also gets "probability" (word_probabilities). token_alternatives (one list of [id, lp] per token):
+    every word dict also gets "alternatives", one rendered list per token of the word (render_alternatives)."""
     language = language or "english"
     if language in {"chinese", "japanese", "thai", "lao", "myanmar", "cantonese"}:
         words, wtoks, idx = _split_tokens_on_unicode(vocab, tokens)
@@ -304,7 +306,18 @@ def collate_word_timestamps(vocab: "WhisperVocab", tokens: List[int], token_time
     if token_logprobs is not None:
         for d, p in zip(out, word_probabilities(idx, token_logprobs)):
             d["probability"] = p
+    if token_alternatives is not None:
+        for d, ix in zip(out, idx):
+            d["alternatives"] = [render_alternatives(vocab, token_alternatives[k]) for k in ix]
     return out
+
+
+def render_alternatives(vocab: "WhisperVocab", alts: Sequence) -> List[dict]:
+    """One token's alternatives [[id, lp], ...] as [{"id", "text", "logprob"}, ...]: a text id rendered with
+    vocab.decode, a special or timestamp id with its token string."""
+    tsb, special = vocab.special.timestamp_begin, vocab.all_special_ids
+    return [{"id": int(i), "text": vocab.id_to_token[int(i)] if (int(i) >= tsb or int(i) in special)
+             else vocab.decode([int(i)]), "logprob": float(lp)} for i, lp in alts]
 
 
 def word_probabilities(token_indices: Sequence[Sequence[int]], token_logprobs: Sequence[float]) -> List[float]:
@@ -328,8 +341,12 @@ class AsrStitcher:
 
     def __init__(self, vocab: WhisperVocab, return_timestamps, return_language: bool = False,
                  time_precision: float = 0.02, segment_size: int = 1500, state: Optional[dict] = None,
-                 confidence: bool = False):
-        """confidence: every output carries "token_logprobs" (one float per entry of "tokens"); they ride beside
+                 confidence: bool = False, alternatives: bool = False):
+        """alternatives (word timestamps): every output carries "token_alternatives" (per entry of "tokens" a list of
+        [id, lp]); they ride through the stitching like the log-probabilities and come out as each word's
+        "alternatives". The value carried per text token is any plain JSON datum: the log-probability alone (a
+        float, as ever), the alternatives alone (a list), or [log-probability, alternatives] with both.
+        confidence: every output carries "token_logprobs" (one float per entry of "tokens"); they ride beside
         the text tokens through the stitching (never compared) and come out as each word's "probability", each
         chunk's "avg_logprob" or the result's "avg_logprob" (assemble_asr). Text, timestamps and chunk boundaries
         are those of the same outputs without it."""
@@ -337,8 +354,10 @@ class AsrStitcher:
         self.time_precision, self.segment_size = time_precision, segment_size
         self.word = return_timestamps == "word"
         self.conf = bool(confidence)
+        self.alt = bool(alternatives)
+        self.aux = self.conf or self.alt
         self.chunks: List[dict] = []  # closed chunks, in order
-        st = state or self.initial_state(confidence=self.conf)
+        st = state or self.initial_state(confidence=self.aux)
         self.previous_token_aux = [list(t) for t in st.get("previous_token_aux", [])]
         self.chunk = {"language": st["chunk"]["language"], "timestamp": list(st["chunk"]["timestamp"]),
                       "text": st["chunk"]["text"]}
@@ -361,16 +380,20 @@ class AsrStitcher:
                 "previous_tokens": [list(t) for t in self.previous_tokens],
                 "previous_token_timestamps": [[tuple(x) for x in t] for t in self.previous_token_timestamps],
                 "skip": self.skip, "last_language": self.last_language, "time_offset": self.time_offset,
-                **({"previous_token_aux": [list(t) for t in self.previous_token_aux]} if self.conf else {})}
+                **({"previous_token_aux": [list(t) for t in self.previous_token_aux]} if self.aux else {})}
 
     def _resolve(self, chunk: dict, with_ts: bool) -> None:
         """Close `chunk` over the pending token runs: its text, (word) its words, (confidence) its resolved tokens'
         log-probabilities under "_lp" (assemble_asr turns them into the public keys)."""
         vocab = self.vocab
-        if self.conf:
-            resolved, resolved_ts, lps = find_longest_common_sequence(
+        alts = None
+        if self.aux:
+            resolved, resolved_ts, aux = find_longest_common_sequence(
                 self.previous_tokens, self.previous_token_timestamps if with_ts else None, self.previous_token_aux)
-            chunk["_lp"] = lps
+            lps = ([a[0] for a in aux] if self.alt else aux) if self.conf else None
+            alts = ([a[1] for a in aux] if self.conf else aux) if self.alt else None
+            if self.conf:
+                chunk["_lp"] = lps
         elif with_ts:
             resolved, resolved_ts = find_longest_common_sequence(self.previous_tokens, self.previous_token_timestamps)
             lps = None
@@ -379,7 +402,7 @@ class AsrStitcher:
         chunk["text"] = vocab.decode(resolved)
         if with_ts and self.word:
             chunk["words"] = collate_word_timestamps(vocab, resolved, resolved_ts, self.last_language,
-                                                     self.return_language, lps)
+                                                     self.return_language, lps, alts)
 
     def _new_chunk(self) -> dict:
         return {"language": self.last_language, "timestamp": [None, None], "text": ""}
@@ -398,6 +421,10 @@ class AsrStitcher:
         if self.conf:  # (cut with a stripped prompt: one value per remaining token)
             token_lps = list(output["token_logprobs"])
             token_lps = token_lps[len(token_lps) - len(token_ids):] if token_ids else []
+        token_alts = None
+        if self.alt:
+            token_alts = list(output["token_alternatives"])
+            token_alts = token_alts[len(token_alts) - len(token_ids):] if token_ids else []
         last_timestamp = None
         first_timestamp = timestamp_begin
         cur_max_timestamp = 0.0
@@ -476,7 +503,10 @@ class AsrStitcher:
                         chunk = self._new_chunk()
             else:
                 current_tokens.append(token)
-                if token_lps is not None:
+                if token_alts is not None:  # (lists, not tuples: a state travels as JSON)
+                    a = [[int(t), float(lp)] for t, lp in token_alts[i]]
+                    current_aux.append([float(token_lps[i]), a] if token_lps is not None else a)
+                elif token_lps is not None:
                     current_aux.append(float(token_lps[i]))
                 if word:
                     start = (round(0.0 + self.time_offset, 2) if i == 0
@@ -539,12 +569,13 @@ def assemble_asr(chunks: List[dict], return_timestamps, return_language: bool,
 
 
 def decode_asr(vocab: WhisperVocab, outputs: Sequence[dict], return_timestamps, return_language: bool = False,
-               time_precision: float = 0.02, segment_size: int = 1500, confidence: bool = False) -> Tuple[str, dict]:
+               time_precision: float = 0.02, segment_size: int = 1500, confidence: bool = False,
+               alternatives: bool = False) -> Tuple[str, dict]:
     """outputs: [{"tokens": [ids...], "stride": (chunk_len_s, left_s, right_s) optional,
-    "token_timestamps": [s...] (return_timestamps="word"), "token_logprobs": [lp...] (confidence)}, ...] in chunk
-    order."""
+    "token_timestamps": [s...] (return_timestamps="word"), "token_logprobs": [lp...] (confidence),
+    "token_alternatives": [[[id, lp], ...], ...] (alternatives)}, ...] in chunk order."""
     stitcher = AsrStitcher(vocab, return_timestamps, return_language, time_precision, segment_size,
-                           confidence=confidence)
+                           confidence=confidence, alternatives=alternatives)
     for output in outputs:
         stitcher.feed(output)
     return stitcher.finish()
