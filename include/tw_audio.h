@@ -22,6 +22,8 @@
  *   tw_resample_pcm_i32 / _f32       downmix + polyphase resample on the GPU (DEVICE memory, `stream`), the
  *                                    libswresample default filter restated (Kaiser-windowed sinc, see
  *                                    twamd/audio.py: swr_filter_bank)
+ *   tw_gather_windows                a batch's zero-padded 30-s rows out of a call's concatenated waveforms
+ *                                    (DEVICE memory, `stream`; one launch per engine batch)
  *
  * Conventions as tw_whisper.h: 0 = success, nonzero = failure with tw_last_error() set.
  */
@@ -67,6 +69,18 @@ int tw_resample_pcm_i32(const int32_t* pcm, int64_t n_in, int32_t channels, floa
                         const float* taps, int32_t ntaps, float* y, int64_t n_out, void* stream);
 int tw_resample_pcm_f32(const float* x, int64_t n_in, int32_t channels, int32_t up, int32_t down, const float* taps,
                         int32_t ntaps, float* y, int64_t n_out, void* stream);
+
+/* One engine batch's waveform rows out of the call's arena (the 16 kHz mono f32 waveforms of a call's inputs,
+ * concatenated in device memory), in one launch:
+ *   out[j][i] = i < length[j] ? arena[start[j] + i] : 0.0f   for 0 <= j < rows, 0 <= i < row_len.
+ * arena: f32[arena_len] DEVICE. out: f32 rows of out_stride floats, DEVICE. start / length: HOST arrays, read
+ * during the call (they travel as kernel arguments, at most 64 rows per launch; more rows = more launches).
+ * Checked on the host before anything is launched: rows >= 0, 0 <= length[j] <= row_len <= out_stride,
+ * start[j] >= 0, start[j] + length[j] <= arena_len. Reads no arena element outside [start[j], start[j]+length[j]),
+ * writes nothing outside out[j][0 .. row_len). No allocation, no synchronisation. 16-byte stores when every out
+ * row is 16-byte aligned, 16-byte loads for the rows whose arena + start[j] is. */
+int tw_gather_windows(const float* arena, int64_t arena_len, const int64_t* start, const int32_t* length,
+                      int32_t rows, int64_t row_len, float* out, int64_t out_stride, void* stream);
 
 /* G.711 expansion of n codes to s16 (HOST memory): mu-law (alaw == 0) or A-law, the classic ITU-T G.711 tables
  * (WAV format tags 7 / 6, AU encodings 1 / 27, AIFF-C 'ulaw' / 'alaw'; what ffmpeg_read's pcm_mulaw / pcm_alaw give). */

@@ -59,6 +59,7 @@ EXPORTED = (
     "tw_dec_fused_set_grid", "tw_dec_fused_set_acquire", "tw_dec_fused_set_probe", "tw_dec_fused_grid",
     "tw_dec_fused_xpart_bytes", "tw_logits_history", "tw_token_logprob", "tw_logits_sample_lp",
     "tw_logits_history_bias", "tw_logits_force", "tw_align_cost", "tw_token_topk_workspace_bytes", "tw_token_topk",
+    "tw_gather_windows",
 )
 
 
@@ -232,6 +233,7 @@ _SIGS = {
                         ctypes.POINTER(ctypes.c_int64)], _I),
     "tw_resample_pcm_i32": ([_P, ctypes.c_int64, _I, _F, _I, _I, _P, _I, _P, ctypes.c_int64, _P], _I),
     "tw_resample_pcm_f32": ([_P, ctypes.c_int64, _I, _I, _I, _P, _I, _P, ctypes.c_int64, _P], _I),
+    "tw_gather_windows": ([_P, ctypes.c_int64, _P, _P, _I, ctypes.c_int64, _P, ctypes.c_int64, _P], _I),
     "tw_dec_fused": ([_P, _I, _I, _P, _P, _P, _P, _L, _I, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P,
                       _P], _I),
     "tw_dec_fused_xpart_bytes": ([_I], ctypes.c_size_t),

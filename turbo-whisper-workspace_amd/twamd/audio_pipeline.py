@@ -208,6 +208,43 @@ class AudioProcessingPipeline:
             print(f"Error during transcription: {e}")
             return {"error": f"Transcription error: {str(e)}"}
 
+    def transcribe_many(self, audio_paths: List[str], task: str = "transcribe",
+                        return_timestamps: bool = True) -> List[Dict[str, Any]]:
+        """Extension (the reference has none): transcribe()'s exact call on a list of files, as ONE list call, so
+        the files' windows share engine batches. One result per path, in order, with transcribe()'s error
+        convention per file: every path is decoded first, a file that fails gets {"error": "Transcription error:
+        ..."} at its index, the others go to the engine as 16 kHz arrays; if that call raises, each of them gets
+        the error dict. Not under a collective path (the followers of a RankZeroFrontend hold no files)."""
+        from . import dist
+
+        if dist.collective_path():
+            raise NotImplementedError("transcribe_many is not sharded: call it in a single process")
+        if self.transcription_model is None:
+            if not self.load_transcription_model():
+                return [{"error": "Failed to load transcription model"} for _ in audio_paths]
+        results: List[Optional[Dict[str, Any]]] = [None] * len(audio_paths)
+        waves, where = [], []
+        dev = getattr(getattr(self.transcription_model, "engine", None), "device", None)
+        for i, path in enumerate(audio_paths):
+            try:
+                waves.append(audio.load_input(path, audio.TARGET_SR, dev))
+                where.append(i)
+            except Exception as e:
+                print(f"Error during transcription: {e}")
+                results[i] = {"error": f"Transcription error: {str(e)}"}
+        if waves:
+            try:
+                outs = self.transcription_model(waves, chunk_length_s=60,
+                                                batch_size=512 if self.gpu_available else 32, stride_length_s=5,
+                                                generate_kwargs={"task": task}, return_timestamps=return_timestamps)
+                for i, out in zip(where, outs):
+                    results[i] = out
+            except Exception as e:
+                print(f"Error during transcription: {e}")
+                for i in where:
+                    results[i] = {"error": f"Transcription error: {str(e)}"}
+        return results
+
     def _merge_transcription_with_diarization(self, transcription, diarization_segments):
         """:690-726. With no diarization segments: alternating speakers over the transcript chunks, whose
         `start`/`end` keys HF chunks do not carry (the reference reads them with .get(..., 0))."""

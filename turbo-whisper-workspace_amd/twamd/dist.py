@@ -172,6 +172,29 @@ def broadcast_waveform(wav: Optional[np.ndarray], device: Optional[torch.device]
     return buf if as_tensor else buf.cpu().numpy()
 
 
+def broadcast_lengths(lengths: Optional[Sequence[int]], n: int, device: Optional[torch.device] = None, src: int = 0,
+                      group=None, failed: bool = False, force_collective: Optional[bool] = None) -> List[int]:
+    """A list call's per-input sample counts (rank `src` decoded the n inputs): every rank returns them, from one
+    small int64 broadcast. `failed` (meaningful on `src`): decoding raised there. Every slot then carries -1, as
+    broadcast_waveform's length slot does: `src` gets [] back (and re-raises its own error), every other rank
+    raises PeerError, so no rank waits for the arena."""
+    rank, ws = world()
+    if not collective_path(force_collective):
+        return list(lengths or [])
+    device = _coll_device(device, group)
+    vals = [-1] * n if (rank != src or failed) else [int(x) for x in lengths]
+    if len(vals) != n:
+        raise ValueError(f"{len(vals)} lengths for {n} inputs")
+    t = torch.tensor(vals, dtype=torch.int64, device=device)
+    dist.broadcast(t, src=src, group=group)
+    out = t.cpu().tolist()
+    if any(x < 0 for x in out):
+        if rank == src:
+            return []
+        raise PeerError(f"rank {src} failed to decode the inputs")
+    return out
+
+
 def transcribe_sharded(run_windows, wav: np.ndarray, windows: Sequence, device: Optional[torch.device] = None,
                        group=None, timed: bool = False, force_collective: Optional[bool] = None) -> List:
     """Every rank calls this with the same `windows` (chunk_iter windows over `wav`); each rank runs
@@ -317,15 +340,18 @@ def stitch_sharded(vocab, outputs: Sequence[dict], group=None, force_collective:
 class RankZeroFrontend:
     """Serving on N GPUs: rank 0 owns the request surface (AudioProcessingPipeline / POST /api/transcribe) and
     calls this like the single-GPU callable; the other ranks sit in `follow()`. Each call broadcasts the call's
-    keyword arguments, then every rank enters the SPMD TurboTranscriber.__call__ (rank 0 decodes the input and
-    broadcasts the waveform, windows are sharded, token arrays all-gathered)."""
+    keyword arguments (and a list call's length), then every rank enters the SPMD TurboTranscriber.__call__ (rank 0
+    decodes the input, or every input of a list, and broadcasts the waveform, windows are sharded, token arrays
+    all-gathered)."""
 
     def __init__(self, transcriber, group=None):
         self.transcriber = transcriber
         self.group = group
 
     def __call__(self, inputs, **kwargs):
-        dist.broadcast_object_list([kwargs], src=0, group=self.group)
+        # (a list call: the followers learn its length and call with a list of as many placeholders)
+        n = len(inputs) if isinstance(inputs, list) else None
+        dist.broadcast_object_list([(kwargs, n)], src=0, group=self.group)
         return self.transcriber(inputs, **kwargs)
 
     def close(self) -> None:
@@ -341,8 +367,9 @@ class RankZeroFrontend:
             dist.broadcast_object_list(box, src=0, group=self.group)
             if box[0] is None:
                 return n
+            kwargs, n_inputs = box[0]
             try:
-                self.transcriber(None, **box[0])
+                self.transcriber(None if n_inputs is None else [None] * n_inputs, **kwargs)
             except Exception as e:  # every rank saw the same failure; keep serving
                 print(f"rank {dist.get_rank(self.group)}: call skipped: {e!r}")
                 continue

@@ -13,7 +13,9 @@ AutomaticSpeechRecognitionPipeline preprocess / _forward / postprocess
 """
 from __future__ import annotations
 
+import ctypes
 import os
+from types import SimpleNamespace
 from typing import Any, Dict, List, Optional, Sequence, Union
 
 import numpy as np
@@ -65,6 +67,16 @@ def resolve_decode(gen: GenerationSettings, gk: Dict[str, Any]) -> Dict[str, Any
         ml = gen.max_length if gen.max_length_set else _GLOBAL_DEFAULT_MAX_LENGTH
         mnt = None if ml != _GLOBAL_DEFAULT_MAX_LENGTH else PIPELINE_DEFAULT_MAX_NEW_TOKENS
     return {"num_beams": int(nb) if nb is not None else PIPELINE_DEFAULT_NUM_BEAMS, "max_new_tokens": mnt}
+
+
+def _with_prefix(e: Exception, prefix: str) -> Exception:
+    """An exception of e's type whose message is e's behind `prefix` (e itself, its message rewritten, where the
+    type cannot be built from one string)."""
+    try:
+        return type(e)(prefix + str(e))
+    except Exception:
+        e.args = (prefix + str(e),)
+        return e
 
 
 class TurboTranscriber:
@@ -133,11 +145,14 @@ class TurboTranscriber:
     def __exit__(self, *exc) -> None:
         self.close()
 
-    def __call__(self, inputs: Union[str, bytes, np.ndarray, dict], *, chunk_length_s: float = 0,
+    def __call__(self, inputs: Union[str, bytes, np.ndarray, dict, list], *, chunk_length_s: float = 0,
                  stride_length_s=None, batch_size: int = 1, generate_kwargs: Optional[Dict[str, Any]] = None,
                  return_timestamps: Union[bool, str] = False, return_language: bool = False,
-                 return_confidence: bool = False, return_alternatives: int = 0, **kwargs) -> dict:
-        """The HF ASR pipeline call. return_confidence (extension): the log-probability of every generated token
+                 return_confidence: bool = False, return_alternatives: int = 0,
+                 **kwargs) -> Union[dict, List[dict]]:
+        """The HF ASR pipeline call. A `list` of inputs returns the list of their results, in order, with the
+        windows of all inputs sharing engine batches (_call_list; any other iterable is refused as before).
+        return_confidence (extension): the log-probability of every generated token
         under its step's processed scores (WhisperEngine.generate(token_logprobs=True)) rides through the stitching
         and comes out as each word's "probability" (return_timestamps="word": the mean of exp(lp) over the word's
         tokens, openai-whisper's definition), each chunk's "avg_logprob" (return_timestamps=True) or the result's
@@ -196,6 +211,14 @@ class TurboTranscriber:
         if not st.is_multilingual and (task is not None or language is not None):
             raise ValueError("Cannot specify `task` or `language` for an English-only model.")
 
+        o = SimpleNamespace(word=word, conf=conf, n_alt=n_alt, task=task, language=language, num_beams=num_beams,
+                            max_new_tokens=max_new_tokens, max_passes=max_passes, cond=cond, prompt=prompt,
+                            fallback=fallback, hist=hist, batch_size=batch_size, chunk_length_s=chunk_length_s,
+                            stride_length_s=stride_length_s, return_timestamps=return_timestamps,
+                            return_language=return_language)
+        if isinstance(inputs, list):  # the pipeline's list call: a list of results, engine batches shared
+            return self._call_list(inputs, o)
+
         rank, world = dist.world()
         sharded = dist.collective_path()  # (world > 1, or a forced collective in a world of one)
         dev = getattr(self.engine, "device", None)
@@ -217,14 +240,140 @@ class TurboTranscriber:
                 raise StopIteration
             with_stride = True
         elif len(wav) > CHUNK_SAMPLES:  # long-form: one sequential generate() over the whole input (asr:450-457)
-            return self._long_form(wav, task=task, language=language, return_timestamps=return_timestamps,
-                                   return_language=return_language, max_new_tokens=max_new_tokens,
-                                   num_beams=num_beams, max_passes=max_passes, fallback=fallback, condition=cond,
-                                   prompt=prompt, history=hist, confidence=conf, alternatives=n_alt)
+            return self._long_form(wav, **self._long_form_options(o))
         else:
             windows = [Window(0, len(wav), 0, 0, True)]
             with_stride = False
-        lang_id = self._lang_id(language)
+        model_outputs = self._window_outputs(o, wav, windows, with_stride, sharded)
+        kw = self._stitch_options(o)
+        # sharded: every rank stitches its own windows and the pieces are merged (dist.stitch_sharded: the serial
+        # _decode_asr result, without rank 0 walking every window of the call)
+        text, optional = (dist.stitch_sharded(self.vocab, model_outputs, **kw) if sharded else
+                          decode_asr(self.vocab, model_outputs, **kw))
+        return {"text": text, **optional}
+
+    # the per-window records of the last call (transcribe_windows / _long_form), flat over a list call's windows
+    _WINDOW_RECORDS = ("last_window_langs", "last_window_passes", "last_window_prefixes",
+                       "last_window_token_timestamps", "last_window_pass_logprobs", "last_window_token_logprobs",
+                       "last_window_token_alternatives")
+
+    def _call_list(self, inputs: list, o) -> List[dict]:
+        """The list call (Pipeline.__call__ on a list, $TF/pipelines/base.py:1270-1278): one result per input, in
+        order, every call option applied to every input. Rank 0 decodes every input into one arena (the 16 kHz
+        waveforms, concatenated; device memory on a GPU engine, uploaded once). With chunk_length_s the windows of
+        all inputs form one flat list with arena-absolute starts and go through the engine once, so engine batches
+        (and, where batch composition shapes results, the batch_size groups) cross input boundaries as the
+        pipeline's DataLoader batches do; every input's windows are then stitched on their own. Without it the
+        inputs of at most 30 s are one window each and share batches, and a longer input runs through _long_form
+        alone (the pipeline's result at batch_size=1). An empty element raises ValueError (transformers returns
+        too few results there). last_input_windows: per input (first window, windows) into the flat
+        last_window_* records (a long-form input holds one record, its passes)."""
+        if not inputs:
+            return []
+        rank, _ = dist.world()
+        sharded = dist.collective_path()
+        sr = self.sampling_rate
+        dev = getattr(self.engine, "device", None)
+        waves, load_err = [], None
+        if rank == 0:
+            try:
+                limit, total = audio.max_audio_seconds() * sr, 0
+                for i, x in enumerate(inputs):
+                    try:
+                        w = audio.load_input(x, sr, dev)
+                    except Exception as e:
+                        named = _with_prefix(e, f"inputs[{i}]: ")
+                        raise named from (e if named is not e else None)
+                    if len(w) == 0:
+                        raise ValueError(f"inputs[{i}] is empty")
+                    total += len(w)
+                    if total > limit:
+                        raise ValueError(f"inputs[0..{i}] hold {total / sr:.1f} s, more than TW_MAX_AUDIO_S="
+                                         f"{audio.max_audio_seconds():g} s in one call: split the list")
+                    waves.append(w)
+            except Exception as e:  # raised below, after the other ranks have been told (no rank left waiting)
+                load_err = e
+        arena = None if load_err is not None or rank != 0 else \
+            np.concatenate([np.ascontiguousarray(w, np.float32) for w in waves])
+        lengths = [len(w) for w in waves]
+        if sharded:  # SPMD: every rank calls with a list of the same length; rank 0 decoded it
+            lengths = dist.broadcast_lengths(lengths, len(inputs), failed=load_err is not None)
+            if load_err is None:
+                arena = dist.broadcast_waveform(arena, as_tensor=True)
+        if load_err is not None:
+            raise load_err
+        if not sharded and getattr(dev, "type", None) == "cuda":  # one upload; every batch is gathered out of it
+            arena = torch.from_numpy(arena).to(dev)
+            torch.cuda.current_stream(dev).synchronize()
+        offs = np.cumsum([0] + lengths).tolist()
+        kw = self._stitch_options(o)
+        results: List[Optional[dict]] = [None] * len(inputs)
+        records: List[Optional[Dict[str, list]]] = [None] * len(inputs)  # per input its slice of every last_window_*
+        flat: List[Window] = []
+        spans: Dict[int, tuple] = {}  # input -> (first, count) in `flat`
+        long_inputs: List[int] = []
+        for i, n in enumerate(lengths):
+            if o.chunk_length_s:
+                ws = [w._replace(start=w.start + offs[i])
+                      for w in chunk_windows(n, o.chunk_length_s, o.stride_length_s, sr)]
+            elif n > CHUNK_SAMPLES:
+                long_inputs.append(i)
+                continue
+            else:
+                ws = [Window(offs[i], n, 0, 0, True)]
+            spans[i] = (len(flat), len(ws))
+            flat.extend(ws)
+        for name in self._WINDOW_RECORDS:
+            setattr(self, name, [])
+        if flat:
+            outs = self._window_outputs(o, arena, flat, bool(o.chunk_length_s), sharded)
+            r, world = dist.world()
+            lo, hi = dist.shard_range(len(flat), world, r) if sharded else (0, len(flat))
+            for i, (first, count) in spans.items():
+                text, optional = decode_asr(self.vocab, outs[first: first + count], **kw)
+                results[i] = {"text": text, **optional}
+                # (under a collective path the records are this rank's shard of the flat list, as in a single call)
+                a, b = max(first, lo) - lo, max(min(first + count, hi), lo) - lo
+                records[i] = {name: getattr(self, name)[a: b] for name in self._WINDOW_RECORDS}
+        for i in long_inputs:  # each alone, as a long-form single call (every rank computes it)
+            for name in self._WINDOW_RECORDS:
+                setattr(self, name, [])
+            results[i] = self._long_form(arena[offs[i]: offs[i + 1]], **self._long_form_options(o))
+            records[i] = {name: list(getattr(self, name)) for name in self._WINDOW_RECORDS}
+        self.last_input_windows = []
+        merged: Dict[str, list] = {name: [] for name in self._WINDOW_RECORDS}
+        first = 0
+        for i, rec in enumerate(records):  # (windows of the whole call, also where the records are a rank's shard)
+            count = spans[i][1] if i in spans else len(rec["last_window_passes"])
+            self.last_input_windows.append((first, count))
+            first += count
+            for name in self._WINDOW_RECORDS:
+                merged[name].extend(rec[name])
+        for name, v in merged.items():
+            setattr(self, name, v)
+        return results
+
+    @staticmethod
+    def _long_form_options(o) -> Dict[str, Any]:
+        """_long_form's keyword arguments for a call's options."""
+        return dict(task=o.task, language=o.language, return_timestamps=o.return_timestamps,
+                    return_language=o.return_language, max_new_tokens=o.max_new_tokens, num_beams=o.num_beams,
+                    max_passes=o.max_passes, fallback=o.fallback, condition=o.cond, prompt=o.prompt, history=o.hist,
+                    confidence=o.conf, alternatives=o.n_alt)
+
+    def _stitch_options(self, o) -> Dict[str, Any]:
+        """decode_asr's keyword arguments for a call's options."""
+        return dict(return_timestamps="word" if o.word else bool(o.return_timestamps),
+                    return_language=o.return_language,
+                    time_precision=time_precision(self.engine.d.max_source_positions),
+                    **({"confidence": True} if o.conf else {}), **({"alternatives": True} if o.n_alt else {}))
+
+    def _window_outputs(self, o, wav, windows: Sequence[Window], with_stride: bool, sharded: bool) -> List[dict]:
+        """The windows of a call (of one input, or of every input of a list call: their `start` indexes `wav`)
+        through the engine, sharded over the ranks under a collective path: one model-output dict per window, as
+        decode_asr reads them ("tokens", "stride" with with_stride, the per-token lanes the call's options ask for)."""
+        word, conf, n_alt, cond, fallback, num_beams = o.word, o.conf, o.n_alt, o.cond, o.fallback, o.num_beams
+        lang_id = self._lang_id(o.language)
 
         def run(w, ws):
             base = windows.index(ws[0]) if ws else 0  # this shard's first global window (the sampler's row keys)
@@ -232,13 +381,13 @@ class TurboTranscriber:
             # conditioned prompts — their left padding — and with beams under the fallback — a sampling round turns the
             # rest of that generate() call greedy —, so batch_size is kept there)
             grouped = word or cond or (fallback.active and num_beams > 1)
-            kw = dict(task=task, lang_id=lang_id, return_timestamps=bool(return_timestamps) or word,
-                      max_new_tokens=max_new_tokens, num_beams=num_beams, max_passes=max_passes,
+            kw = dict(task=o.task, lang_id=lang_id, return_timestamps=bool(o.return_timestamps) or word,
+                      max_new_tokens=o.max_new_tokens, num_beams=num_beams, max_passes=o.max_passes,
                       **({"fallback": fallback, "window_base": base} if fallback.active else {}),
                       **({"condition_on_prev_tokens": True} if cond else {}),
-                      **({"prompt": prompt} if prompt else {}),
-                      **({"history": hist} if hist else {}),
-                      **({"group": batch_size} if grouped else {}),
+                      **({"prompt": o.prompt} if o.prompt else {}),
+                      **({"history": o.hist} if o.hist else {}),
+                      **({"group": o.batch_size} if grouped else {}),
                       **({"token_logprobs": True} if conf else {}),
                       **({"top_alternatives": n_alt} if n_alt else {}))
             if word:  # token times ride along as floats after the tokens (one all-gather carries both)
@@ -264,30 +413,23 @@ class TurboTranscriber:
         outputs = dist.transcribe_sharded(run, wav, windows, timed=n_lanes) if sharded else run(wav, windows)
         model_outputs = []
         for w, toks in zip(windows, outputs):
-            o = {}
+            mo = {}
             if n_lanes:
                 toks, *fl = toks
                 if word:
-                    o["token_timestamps"] = fl[0]
+                    mo["token_timestamps"] = fl[0]
                 if conf:
-                    o["token_logprobs"] = fl[int(word)]
+                    mo["token_logprobs"] = fl[int(word)]
                 if n_alt:
                     al = fl[n_lanes - 2 * n_alt:]
-                    o["token_alternatives"] = [[[int(al[2 * j][n]), al[2 * j + 1][n]] for j in range(n_alt)
-                                                if al[2 * j][n] >= 0] for n in range(len(toks))]
-            o["tokens"] = toks
+                    mo["token_alternatives"] = [[[int(al[2 * j][n]), al[2 * j + 1][n]] for j in range(n_alt)
+                                                 if al[2 * j][n] >= 0] for n in range(len(toks))]
+            mo["tokens"] = toks
             if with_stride:
                 sr = self.sampling_rate
-                o["stride"] = (w.length / sr, w.stride_left / sr, w.stride_right / sr)
-            model_outputs.append(o)
-        kw = dict(return_timestamps="word" if word else bool(return_timestamps), return_language=return_language,
-                  time_precision=time_precision(self.engine.d.max_source_positions),
-                  **({"confidence": True} if conf else {}), **({"alternatives": True} if n_alt else {}))
-        # sharded: every rank stitches its own windows and the pieces are merged (dist.stitch_sharded: the serial
-        # _decode_asr result, without rank 0 walking every window of the call)
-        text, optional = (dist.stitch_sharded(self.vocab, model_outputs, **kw) if sharded else
-                          decode_asr(self.vocab, model_outputs, **kw))
-        return {"text": text, **optional}
+                mo["stride"] = (w.length / sr, w.stride_left / sr, w.stride_right / sr)
+            model_outputs.append(mo)
+        return model_outputs
 
     def align(self, inputs: Union[str, bytes, np.ndarray, dict], chunks: Sequence[dict], *,
               language: Optional[str] = None, task: Optional[str] = None, batch_size: Optional[int] = None,
@@ -468,7 +610,9 @@ class TurboTranscriber:
         (last_window_pass_logprobs beside last_window_passes, last_window_token_logprobs beside the returned tokens,
         unpadded). top_alternatives: likewise every token's alternatives (last_window_token_alternatives).
 
-        wav: a host array, or a torch tensor (a rank's copy of the broadcast waveform, in device memory)."""
+        wav: a host array (staged and uploaded batch by batch), or a torch tensor: in GPU memory (a rank's copy of
+        the broadcast waveform, a list call's arena) every batch's rows are gathered out of it by one
+        tw_gather_windows launch; a CPU tensor (gloo) is sliced."""
         eng = self.engine
         if group:
             B = max(1, min(int(group), eng.max_batch))
@@ -478,10 +622,20 @@ class TurboTranscriber:
         offs = np.cumsum([0] + sizes).tolist()
         parts = [windows[offs[k]: offs[k + 1]] for k in range(len(sizes))]
         on_device = torch.is_tensor(wav)
+        on_gpu = on_device and wav.is_cuda
+        if on_gpu and (wav.dtype != torch.float32 or not wav.is_contiguous()):
+            wav = wav.to(torch.float32).contiguous()
 
         def load(k):  # called on the engine's encoder stream
             part = parts[k]
-            if on_device:  # device-to-device slices of the rank's waveform copy
+            if on_gpu:  # one launch gathers the batch's rows out of the waveform (the arena) in device memory
+                n = len(part)
+                start = (ctypes.c_int64 * n)(*[int(w.start) for w in part])
+                length = (ctypes.c_int32 * n)(*[min(int(w.length), CHUNK_SAMPLES) for w in part])  # fe truncation
+                _lib.call("tw_gather_windows", wav.data_ptr(), wav.numel(), start, length, n, CHUNK_SAMPLES,
+                          eng.wave.data_ptr(), eng.wave.stride(0), torch.cuda.current_stream(wav.device).cuda_stream)
+                return
+            if on_device:  # a CPU tensor (gloo): slices of the rank's waveform copy
                 dst = eng.wave[: len(part)]
                 for j, w in enumerate(part):
                     n = min(w.length, CHUNK_SAMPLES)  # feature extractor truncation
